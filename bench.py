@@ -13,8 +13,14 @@ Workload: config E's mesh — unit cube, 203^3 cubes x 6 Kuhn tetrahedra = 50,19
 cube into z-slabs (strong scaling: fixed total mesh); by default each rank also assembles the cell
 layer above its slab (ghost mode: its owned rows complete with no data-path collective), or, with
 --slab-mode exchange, shared slab-interface rows are summed with an RCCL exchange between slab
-neighbours (femasm.parallel). At N = 1 with config E the line also carries an "eneo" block: the
-neo-Hookean AD tangent (config E's physics) timed on the same mesh in the same process.
+neighbours (femasm.parallel).
+
+A plain run does what the headline figure needs and no more: setup, warmup, the timed steps, the
+result line. --full adds the secondary measurements to the same line: the measured HBM stream peak
+(roofline.peak_measured), the CPU baseline (cpu_baseline) and, at N = 1 with config E, the "eneo"
+block: the neo-Hookean AD tangent (config E's physics) timed on the same mesh in the same process.
+--dump-outputs DIR writes what the last timed step left in the matrix (N = 1), so two builds can be
+compared value for value.
 
 Prints ONE JSON line (rank 0).
 """
@@ -297,6 +303,45 @@ def cpu_baseline(sample_n: int, reps: int):
     return m.num_cells / t / 1e6, m.num_cells, t
 
 
+DUMP_MAX_BYTES = 60_000_000  # of array data per --dump-outputs (three small .npy headers on top)
+DUMP_SEED = 20240607
+
+
+def dump_outputs(A, out_dir: str) -> dict:
+    """--dump-outputs: what a caller of the timed path receives, the values of A as the last step left
+    them, written as float64 .npy files under out_dir:
+      values.npy           [K, bs, bs]  value blocks
+      block_positions.npy  [K]          their positions in A.indices (ascending)
+      block_columns.npy    [K]          their block columns, A.indices[position]
+    K = every block A holds when that fits DUMP_MAX_BYTES, else a seeded sample without replacement
+    (numpy default_rng(DUMP_SEED)), the same positions in every run on the same pattern."""
+    bs = A.bs
+    offs = [int(A.indptr[r0]) for r0, _, _ in A.parts]  # position in A.indices of each part's first block
+    counts = [int(d.shape[0]) for _, _, d in A.parts]
+    held = sum(counts)
+    cap = DUMP_MAX_BYTES // (8 * (bs * bs + 2))
+    if held <= cap:
+        local = np.arange(held, dtype=np.int64)
+    else:
+        local = np.sort(np.random.default_rng(DUMP_SEED).choice(held, size=cap, replace=False)).astype(np.int64)
+    values = np.empty((local.size, bs, bs), dtype=np.float64)
+    pos = np.empty(local.size, dtype=np.int64)
+    first = 0  # index among the held blocks of this part's first
+    for off, cnt, (_, _, data) in zip(offs, counts, A.parts):
+        i0, i1 = np.searchsorted(local, [first, first + cnt])
+        if i1 > i0:
+            idx = torch.from_numpy(local[i0:i1] - first).to(data.device)
+            values[i0:i1] = data.index_select(0, idx).cpu().numpy()
+            pos[i0:i1] = local[i0:i1] - first + off
+        first += cnt
+    cols = A.indices.index_select(0, torch.from_numpy(pos).to(A.indices.device)).cpu().numpy()
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "values.npy"), values)
+    np.save(os.path.join(out_dir, "block_positions.npy"), pos.astype(np.float64))
+    np.save(os.path.join(out_dir, "block_columns.npy"), cols.astype(np.float64))
+    return {"blocks": int(local.size), "of": held, "sampled": held > cap}
+
+
 def time_steps(step, steps: int, warmup: int, dev, dist=None):
     """W untimed steps, then K steps bracketed by a barrier + synchronize on both sides; returns the
     wall seconds of the K steps and the mean launch time (HIP events on the launch stream, ms)."""
@@ -419,6 +464,12 @@ def main():
     ap.add_argument("--method", default="gather", choices=["gather", "scatter"])
     ap.add_argument("--deterministic", action="store_true",
                     help="bit-reproducible gather (FA_DETERMINISTIC: exact fixed-point sums)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary measurements: the HBM stream probe, the CPU baseline and, at "
+                         "N = 1 with config E, the neo-Hookean block (each still has its own --no-... switch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the matrix values of the last step (all, or a fixed seeded "
+                         "sample of at most 60 MB) as DIR/<name>.npy; single GPU only")
     ap.add_argument("--cpu-sample-n", type=int, default=24)
     ap.add_argument("--cpu-reps", type=int, default=7)
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -440,8 +491,12 @@ def main():
                     help="processes of the all-cores CPU baseline (0 = every affinity core, capped by the cgroup "
                          "CPU quota; 1 = single core only)")
     args = ap.parse_args()
+    if not args.full:  # a plain run: the headline figure only
+        args.no_cpu_baseline = args.no_hbm_probe = args.no_eneo = True
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
+    if args.dump_outputs and world > 1:
+        raise SystemExit("--dump-outputs writes the single-GPU matrix: run it without torchrun")
     # Multi-core CPU baseline workers: the fork server starts before this process touches the GPU
     # (workers must not inherit an initialised HIP runtime); the workers themselves are forked from
     # it only after the GPU timing -- a pool of 256 idle workers alive during the timed steps slowed
@@ -577,6 +632,9 @@ def main():
         # per-launch kernel durations: HIP events on the launch stream (torch's current stream)
         elapsed, launch_ms = time_steps(step, args.steps, args.warmup, dev, dist)
         ncells_total = ncells_local
+        if args.dump_outputs:
+            d = dump_outputs(A, args.dump_outputs)
+            log(f"[bench] wrote {d['blocks']} of {d['of']} value blocks to {args.dump_outputs}")
 
     ms_per_step = elapsed / args.steps * 1e3
     melem_s = ncells_total / (ms_per_step * 1e-3) / 1e6
