@@ -18,6 +18,7 @@ FA_TRIANGLE, FA_QUADRILATERAL, FA_TETRAHEDRON, FA_HEXAHEDRON = 3, 4, -4, 8
 FA_LINEAR_ELASTICITY, FA_ASYM_DAMAGE, FA_NEO_HOOKEAN, FA_ASYM_DAMAGE_AD = 0, 1, 2, 3
 FA_GATHER, FA_SCATTER, FA_ZERO_FIRST, FA_DETERMINISTIC, FA_CHECK_ERRORS = 0x0, 0x1, 0x2, 0x4, 0x8
 FA_PLAN_AFFINE, FA_PLAN_DETERMINISTIC, FA_PLAN_ORDER_SEARCH, FA_PLAN_NEO = 0x1, 0x2, 0x4, 0x8
+FA_EVAL_GRAD, FA_EVAL_STRAIN, FA_EVAL_STRESS, FA_EVAL_ENERGY = 0x1, 0x2, 0x4, 0x8
 
 
 class FemasmError(RuntimeError):
@@ -116,6 +117,7 @@ SIGNATURES = {
     "fa_gather_prepare": (ctypes.c_int, [P, P, P, P, P]),
     "fa_gather_rows": (ctypes.c_int, [P, P, P, P, P, D, P, P, P]),
     "fa_assemble_vector": (ctypes.c_int, [P, P, P, P, P]),
+    "fa_eval_cells": (ctypes.c_int, [P, P, I32, P, P, I64, P, P, P, P, P]),
     "fa_apply_lifting": (ctypes.c_int, [P, P, P, P, P, P, P, D, P]),
     "fa_set_bc": (ctypes.c_int, [P, I64, P, P, P, D, P]),
     "fa_bsr_mult": (ctypes.c_int, [P, P, P, P]),

@@ -296,8 +296,23 @@ class Function:
         return self.x
 
     def interpolate(self, fn):
-        """Nodal interpolation: fn(x[gdim, n]) -> values [bs, n] (dolfinx convention)."""
+        """Nodal interpolation: fn(x[gdim, n]) -> values [bs, n] (dolfinx convention), or an
+        ``Expression`` evaluated at the single interpolation point of a DG0 space
+        (FEniCSx/mechanic2d/asym_elasto_damage_model.cc:926-927: ``stress->interpolate(expr)``)."""
         V = self.function_space
+        if isinstance(fn, Expression):
+            if V.family not in ("DG", "Discontinuous Lagrange") or V.degree != 0:
+                raise ValueError("interpolating an Expression needs a DG0 space")
+            if V.mesh is not fn.form.V.mesh:
+                raise ValueError("the Expression's form lives on another mesh")
+            if V.bs != fn.value_size:
+                raise ValueError(f"space block size {V.bs} != the expression's value size {fn.value_size}")
+            if fn.X.shape[0] != 1 or not np.array_equal(fn.X, interpolation_points(V.mesh.cell_type)):
+                raise ValueError("the Expression's points must be the DG0 space's single interpolation point")
+            if self.x.dtype != torch.float64 or not self.x.is_contiguous() or self.x.numel() != V.num_dofs:
+                self.x = torch.empty(V.num_dofs, dtype=torch.float64, device=V.mesh.device)
+            evaluate(fn.form, (fn.quantity,), X=fn.X, out={fn.quantity: self.x.view(V.num_nodes, V.bs)})
+            return
         xn = V.tabulate_dof_coordinates()
         vals = fn(xn.T)
         vals = torch.as_tensor(vals, dtype=torch.float64, device=xn.device).reshape(V.bs, -1)
@@ -934,3 +949,115 @@ def set_bc(b: torch.Tensor, bcs: list, x0=None, alpha: float = 1.0, scale=None):
     _lib.check(Lb.fa_set_bc(b.data_ptr(), b.numel(), marker.data_ptr(), g.data_ptr(), _lib.ptr(x), float(alpha),
                             _lib.stream_handle(V.mesh.device)), "fa_set_bc")
     return b
+
+
+# ---------------------------------------------------------------------------------- expressions
+QUANTITIES = ("grad", "strain", "stress", "energy")
+
+
+def interpolation_points(ct) -> np.ndarray:
+    """The DG0 interpolation point of a cell type, [1, tdim]: its midpoint (1/3, 1/3),
+    (1/4, 1/4, 1/4), (1/2, 1/2) or (1/2, 1/2, 1/2) (basix DG0 ``element.points``)."""
+    ct = CellType(ct)
+    td = len(_REF_VERTS[ct][0])
+    return np.full((1, td), 1.0 / (td + 1) if is_simplex(ct) else 0.5)
+
+
+def value_size(form, quantity: str) -> int:
+    """Values per point of a quantity: grad gd*gd; strain and the small-strain stress gd(gd+1)/2
+    (reduced: (xx, xy, yy) / (xx, xy, xz, yy, yz, zz)); the neo-Hookean stress (first Piola) gd*gd;
+    energy 1."""
+    gd = form.V.mesh.gdim
+    if quantity not in QUANTITIES:
+        raise ValueError(f"unknown quantity {quantity!r}: one of {QUANTITIES}")
+    if quantity == "energy":
+        return 1
+    if quantity == "grad" or (quantity == "stress" and form.kind == _lib.FA_NEO_HOOKEAN):
+        return gd * gd
+    return gd * (gd + 1) // 2
+
+
+def _check_expression(form, quantities, X) -> np.ndarray:
+    """Host-side argument checks of evaluate / Expression (no device call); returns X [npts, tdim]."""
+    if not isinstance(form, LinearElasticity):
+        raise TypeError("expected a femasm form descriptor (LinearElasticity, AsymDamage, ...)")
+    V = form.V
+    if not quantities:
+        raise ValueError("no quantity requested")
+    for q in quantities:
+        value_size(form, q)
+    if len(set(quantities)) != len(quantities):
+        raise ValueError(f"repeated quantity in {tuple(quantities)}")
+    if form.u is None:
+        raise ValueError("evaluating an expression needs the form's state u")
+    if V.family in ("DG", "Discontinuous Lagrange") or V.bs != V.mesh.gdim:
+        raise ValueError("the form's space must be a vector Lagrange space (bs = gdim)")
+    if form.kind in (_lib.FA_ASYM_DAMAGE, _lib.FA_ASYM_DAMAGE_AD) and \
+            (CellType(V.mesh.cell_type) != CellType.triangle or V.degree != 1):
+        raise ValueError("the damage law is the reference's P1-triangle law: its space must be P1 on triangles")
+    td = V.mesh.tdim
+    X = interpolation_points(V.mesh.cell_type) if X is None else np.ascontiguousarray(X, dtype=np.float64)
+    if X.ndim != 2 or X.shape[1] != td or X.shape[0] < 1:
+        raise ValueError(f"X must be reference points [npts >= 1, {td}]")
+    return X
+
+
+def evaluate(form, quantities, X=None, cells=None, out=None) -> dict:
+    """Per-cell expressions of the form's state u at reference points, one fa_eval_cells launch for
+    all of them (dolfinx ``fem.Expression(...).eval``; the reference evaluates reps(u) and rsig(u) in
+    two passes, FEniCSx/mechanic2d/asym_elasto_damage_model.cc:909-942).
+
+    quantities: names from ``QUANTITIES``; "stress" is the form's own law (linear, damage, first Piola
+    of NeoHookean), "energy" = inner(eps, sigma). X: reference points [npts, tdim] (None: the cell's
+    midpoint, the DG0 interpolation point). cells: cell ids (None: every cell). out: optional
+    {name: preallocated float64 tensor of ncells * npts * value_size elements}, contiguous (offset views
+    are fine). Returns {name: tensor [ncells, npts * value_size]}."""
+    quantities = (quantities,) if isinstance(quantities, str) else tuple(quantities)
+    X = _check_expression(form, quantities, X)
+    V = form.V
+    dev = V.mesh.device
+    if cells is None:
+        nc, cptr = V.mesh.num_cells, None
+    else:
+        cells = torch.as_tensor(cells, device=dev).to(torch.int32).contiguous().reshape(-1)
+        nc, cptr = int(cells.numel()), cells.data_ptr()
+        if nc and (int(cells.min()) < 0 or int(cells.max()) >= V.mesh.num_cells):
+            raise ValueError(f"cells outside [0, {V.mesh.num_cells})")
+    npts = int(X.shape[0])
+    res, ptrs = {}, {}
+    for q in quantities:
+        w = npts * value_size(form, q)
+        t = None if out is None else out.get(q)
+        if t is None:
+            t = torch.empty((nc, w), dtype=torch.float64, device=dev)
+        elif t.dtype != torch.float64 or t.device != dev or not t.is_contiguous() or t.numel() != nc * w:
+            raise ValueError(f"out[{q!r}] must be a contiguous float64 tensor of {nc * w} elements on {dev}")
+        res[q] = t.view(nc, w)
+        ptrs[q] = t.data_ptr()
+    # (the neo-Hookean energy goes to the library, which refuses it with FA_E_UNSUPPORTED)
+    if nc == 0 and not (form.kind == _lib.FA_NEO_HOOKEAN and "energy" in quantities):
+        return res  # nothing to launch
+    fm = V._fa_mesh()
+    ff = _fa_form(form)
+    _lib.check(_lib.load().fa_eval_cells(
+        ctypes.byref(fm), ctypes.byref(ff), npts, X.ctypes.data, cptr, nc, ptrs.get("grad"), ptrs.get("strain"),
+        ptrs.get("stress"), ptrs.get("energy"), _lib.stream_handle(dev)), "fa_eval_cells")
+    return res
+
+
+class Expression:
+    """dolfinx.fem.Expression for the expressions the reference's UFL files end with
+    (FEniCSx/mechanic2d/asym_manual.py:103-116: ``(reps(u), centre), (rsig(u), centre), (energ(u),
+    centre)``): one quantity of a form's state at the reference points X (None: the cell midpoint)."""
+
+    def __init__(self, form, quantity: str, X=None):
+        self.X = _check_expression(form, (quantity,), X)
+        self.form = form
+        self.quantity = quantity
+        self.value_size = value_size(form, quantity)
+
+    def eval(self, mesh=None, cells=None) -> torch.Tensor:
+        """Values [ncells, npts * value_size] (dolfinx ``Expression.eval(mesh, cells)``)."""
+        if mesh is not None and mesh is not self.form.V.mesh:
+            raise ValueError("the Expression's form lives on another mesh")
+        return evaluate(self.form, (self.quantity,), X=self.X, cells=cells)[self.quantity]

@@ -76,8 +76,9 @@ def _data_item(item: ET.Element, base: str) -> np.ndarray:
 
 class XDMFFile:
     """dolfinx.io.XDMFFile(comm, path, mode) on one process: ``read_mesh(name)``,
-    ``read_meshtags(mesh, name)``; ``write_mesh(mesh, name)``, ``write_meshtags(tags, mesh)`` (ASCII
-    heavy data; the file is written on close / leaving the ``with`` block)."""
+    ``read_meshtags(mesh, name)``, ``read_function(name)``; ``write_mesh(mesh, name)``,
+    ``write_meshtags(tags, mesh)``, ``write_function(f, t)`` (ASCII heavy data; the file is written on
+    close / leaving the ``with`` block)."""
 
     def __init__(self, path: str, mode: str = "r"):
         if mode not in ("r", "w"):
@@ -217,6 +218,53 @@ class XDMFFile:
                 tt = "Triangle" if ev.shape[1] == 3 else "Quadrilateral"
         self._grids.append(("tags", tags.name, tt, ev, tags.values.cpu().numpy()))
 
+    def write_function(self, f, t: float = 0.0):
+        """dolfinx ``XDMFFile.write_function(f, t)`` for the fields the reference writes after its solve
+        (FEniCSx/mechanic2d/asym_elasto_damage_model.cc:972-982: displacement, strain, stress): a grid named
+        after the function with the mesh and one Attribute. DG0 functions are cell data (``Center="Cell"``,
+        Scalar / Vector / Tensor6 for block sizes 1 / 2-3 / 6); P1 Lagrange functions are vertex data
+        (``Center="Node"``, 2-D vectors padded to 3 components as dolfinx does). Other spaces:
+        NotImplementedError."""
+        if self.mode != "w":
+            raise ValueError("file opened for reading")
+        V = f.function_space
+        mesh, bs = V.mesh, V.bs
+        if V.family in ("DG", "Discontinuous Lagrange") and V.degree == 0:
+            center = "Cell"
+            atype = {1: "Scalar", 2: "Vector", 3: "Vector", 6: "Tensor6"}.get(bs)
+            if atype is None:
+                raise NotImplementedError(f"DG0 function of block size {bs}: XDMF has Scalar, Vector (2-3) and Tensor6")
+        elif V.family in ("Lagrange", "P", "Q", "CG") and V.degree == 1:
+            center = "Node"
+            atype = "Scalar" if bs == 1 else "Vector"
+            if bs > 3:
+                raise NotImplementedError(f"P1 function of block size {bs}")
+        else:
+            raise NotImplementedError(f"write_function: {V.family} degree {V.degree} (DG0 and P1 Lagrange functions only)")
+        vals = f.x.detach().cpu().numpy().astype(np.float64).reshape(-1, bs)
+        if center == "Node" and bs == 2:
+            vals = np.concatenate([vals, np.zeros((vals.shape[0], 1))], axis=1)
+        ct = CellType(mesh.cell_type)
+        cells = mesh.cells.cpu().numpy().astype(np.int64)
+        if ct in _PERM:
+            cells = cells[:, _PERM[ct]]
+        if not hasattr(self, "_x"):
+            self._x = mesh.x.cpu().numpy()
+        self._grids.append(("function", f.name, ct, cells, (center, atype, vals, float(t))))
+
+    def read_function(self, name: str):
+        """(center, values) of the function grid ``name`` written by ``write_function``: "Cell" or
+        "Node" and a float64 array [entities, components] (components as stored: padded P1 vectors
+        come back with 3)."""
+        for g in self._grid_list + [s for g in self._grid_list for s in g.findall("Grid")]:
+            if g.get("Name") != name:
+                continue
+            for att in g.findall("Attribute"):
+                if att.get("Name") == name and att.find("DataItem").get("NumberType", "Float") == "Float":
+                    vals = _data_item(att.find("DataItem"), self._base).astype(np.float64)
+                    return att.get("Center", "Node"), vals.reshape(vals.shape[0], -1)
+        raise KeyError(f"{self.path}: no function named {name!r}")
+
     @staticmethod
     def _item(parent, arr: np.ndarray, number: str):
         it = ET.SubElement(parent, "DataItem", Dimensions=" ".join(str(d) for d in arr.shape), Format="XML")
@@ -237,7 +285,7 @@ class XDMFFile:
         dom = ET.SubElement(root, "Domain")
         for kind, name, ct, top, vals in self._grids:
             g = ET.SubElement(dom, "Grid", Name=name, GridType="Uniform")
-            tname = _TOPO_NAME[ct] if kind == "mesh" else ct
+            tname = ct if kind == "tags" else _TOPO_NAME[ct]
             t = ET.SubElement(g, "Topology", TopologyType=tname, NumberOfElements=str(top.shape[0]),
                               NodesPerElement=str(top.shape[1]))
             self._item(t, top, "Int")
@@ -246,5 +294,10 @@ class XDMFFile:
             if kind == "tags":
                 a = ET.SubElement(g, "Attribute", Name=name, AttributeType="Scalar", Center="Cell")
                 self._item(a, vals.reshape(-1, 1), "Int")
+            elif kind == "function":
+                center, atype, fvals, t = vals
+                ET.SubElement(g, "Time", Value=repr(t))
+                a = ET.SubElement(g, "Attribute", Name=name, AttributeType=atype, Center=center)
+                self._item(a, fvals, "Float")
         ET.ElementTree(root).write(self.path, xml_declaration=True, encoding="utf-8")
         self._grids = []

@@ -313,6 +313,34 @@ int fa_apply_lifting(const fa_mesh* mesh, const fa_form* form, const fa_adjacenc
 int fa_set_bc(double* b, int64_t ndofs, const int8_t* bc, const double* g, const double* x0, double alpha,
               void* stream);
 
+/* Per-cell expressions of the state: the reference's post-processing step, create_expression +
+ * Function::interpolate into a DG0 space (FEniCSx/mechanic2d/asym_elasto_damage_model.cc:909-942, its
+ * timing column 8.1) and MFEM's strainTensor / stressTensor coefficients projected on a DG space
+ * (MFEM/mechanic2d/asym_elasto_damage_model.cc:332-457). Quantities (fa_version() >= 101): */
+#define FA_EVAL_GRAD   0x1  /* grad u, row-major [gd][gd]: du_i/dx_j */
+#define FA_EVAL_STRAIN 0x2  /* sym grad u, reduced: 2-D (xx, xy, yy); 3-D (xx, xy, xz, yy, yz, zz); tensor shear, not engineering */
+#define FA_EVAL_STRESS 0x4  /* the form's law at w = 1: reduced Cauchy stress (same order) for FA_LINEAR_ELASTICITY,
+                               FA_ASYM_DAMAGE, FA_ASYM_DAMAGE_AD; first Piola P row-major [gd][gd] for FA_NEO_HOOKEAN */
+#define FA_EVAL_ENERGY 0x8  /* inner(eps, sigma), 1 value (small-strain laws; FA_NEO_HOOKEAN: FA_E_UNSUPPORTED) */
+/* One launch evaluates every quantity whose output pointer is not NULL (grad u is shared) at the npts
+ * reference points X of the cells cells[0 .. ncells_out) (ids in [0, mesh->ncells), not checked; NULL =
+ * cells 0 .. ncells_out-1). Each output is [ncells_out][npts][value size], contiguous, 8-B aligned;
+ * position k holds cell cells[k]. form->u is required (FA_E_ARG). Material per cell (E / nu or lam / mu);
+ * the damage at a point is sum_a phi_a(X) d_a with the P1 basis (0 when form->d is NULL); the damage
+ * kinds are P1-triangle only (FA_E_UNSUPPORTED otherwise). Every supported cell and degree, affine or
+ * not: the Jacobian is taken at the point from the geometry basis. One lane per cell, no atomics:
+ * deterministic. The tables at X are uploaded once per call (that upload waits for `stream`); for the
+ * cell's single DG0 interpolation point (its midpoint) they are cached, and the call is asynchronous
+ * and allocates nothing. Outputs of at most 16 doubles per cell and quantity, and 24 over all
+ * quantities (every DG0 case) are stored coalesced, 16 B per lane; larger ones through plain per-lane
+ * stores (the slow path). */
+int fa_eval_cells(const fa_mesh* mesh, const fa_form* form,
+                  int32_t npts, const double* X /* HOST [npts][tdim] reference points */,
+                  const int32_t* cells /* device [ncells_out] cell ids, or NULL = cells 0..ncells_out-1 */,
+                  int64_t ncells_out,
+                  double* grad, double* strain, double* stress, double* energy, /* device; each may be NULL */
+                  void* stream);
+
 /* y = A x (block rows of A's window; x, y blocked dof vectors). The Krylov kernel of the Newton
  * driver that consumes the assembled matrix (the reference solves with CG + BoomerAMG,
  * FEniCSx/mechanic2d/asym_elasto_damage_model.cc:717-813). */
