@@ -7,14 +7,15 @@
 // and the device laws of femasm.hip (damage_stress, damage_stress_ad, neo_stress_ad, the geometry) are
 // used here, not copied.
 //
-// fa_version is this file's (101: fa_eval_cells present); femasm.hip's own definition is compiled
-// under another, hidden name.
+// fa_version is this file's (101: fa_eval_cells present; 102: the matrix-free Jacobian action of
+// femasm_apply.hip, included at the end of this file); femasm.hip's own definition is compiled under
+// another, hidden name.
 #include "../../include/femasm.h"
 #define fa_version __attribute__((visibility("hidden"))) fa_version_assembly
 #include "femasm.hip"
 #undef fa_version
 
-extern "C" int fa_version(void) { return 101; }
+extern "C" int fa_version(void) { return 102; }
 
 // ------------------------------------------------------------------------------------ expressions
 constexpr int EV_LIN = 0, EV_DAMAGE = 1, EV_NEO = 2;
@@ -331,3 +332,6 @@ extern "C" int fa_eval_cells(const fa_mesh* mesh, const fa_form* form, int32_t n
   if (tmp) HIP_TRY(hipFreeAsync(tmp, s));
   return rc;
 }
+
+// ------------------------------------------------------------------------------------ matrix-free Jacobian action
+#include "femasm_apply.hip"

@@ -14,6 +14,7 @@ LIB_PATH = os.path.join(_HERE, "lib", "libfemasm.so")
 CSRC = os.path.join(os.path.dirname(_HERE), "csrc")
 
 FA_OK = 0
+FA_E_ARG, FA_E_UNSUPPORTED, FA_E_HIP, FA_E_PATTERN, FA_E_CAPACITY = -1, -2, -3, -4, -5
 FA_TRIANGLE, FA_QUADRILATERAL, FA_TETRAHEDRON, FA_HEXAHEDRON = 3, 4, -4, 8
 FA_LINEAR_ELASTICITY, FA_ASYM_DAMAGE, FA_NEO_HOOKEAN, FA_ASYM_DAMAGE_AD = 0, 1, 2, 3
 FA_GATHER, FA_SCATTER, FA_ZERO_FIRST, FA_DETERMINISTIC, FA_CHECK_ERRORS = 0x0, 0x1, 0x2, 0x4, 0x8
@@ -122,6 +123,10 @@ SIGNATURES = {
     "fa_set_bc": (ctypes.c_int, [P, I64, P, P, P, D, P]),
     "fa_bsr_mult": (ctypes.c_int, [P, P, P, P]),
     "fa_bsr_block_diag": (ctypes.c_int, [P, P, P]),
+    "fa_apply_jacobian": (ctypes.c_int, [P, P, P, P, P, D, P, P, P]),
+    "fa_jacobian_block_diag": (ctypes.c_int, [P, P, P, P, D, P, P]),
+    "fa_apply_plan_bytes": (ctypes.c_int, [P, P, P, P, P]),
+    "fa_apply_plan": (ctypes.c_int, [P, P, P, I64, P]),
     "fa_hbm_probe": (ctypes.c_int, [I32, P, P, I64, P]),
 }
 

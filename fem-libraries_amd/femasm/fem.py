@@ -799,6 +799,139 @@ def assemble_matrix(a, bcs=None, diagonal: float = 1.0, A: MatrixCSR | None = No
     return A
 
 
+class JacobianOperator:
+    """The Jacobian of a form at its current state, applied without assembling it: ``mult(x)`` is
+    ``assemble_matrix(a, bcs, diagonal).mult(x)`` (fa_apply_jacobian) and ``block_diagonal()`` that
+    matrix's diagonal blocks (fa_jacobian_block_diag), with ``MatrixCSR``'s signatures, so it drops into
+    ``nls.KrylovSolver``. The form's ``u`` is read live (same storage): the operator always acts at the
+    current state and needs no re-assembly between Newton steps.
+
+    method: "auto" runs the planned kernel where the element has one (P1 / P2 triangles and tetrahedra)
+    and the generic node-parallel kernel elsewhere, or when a node has more cells than a chunk's tile
+    holds (FA_E_CAPACITY); "planned" raises instead of falling back; "generic" always runs the generic
+    kernel. The apply plan is built once per space and cached on V (like the adjacency).
+    ``num_chunks`` / ``plan_bytes``: the plan's chunks and device bytes (0 for the generic kernel);
+    ``redundancy``: cell visits per launch / cells (1.0 when no cell straddles chunks; nodes per cell
+    for the generic kernel, which visits a cell once per node). Single GPU: ``parallel.SlabProblem``
+    keeps assembling."""
+
+    def __init__(self, a, bcs=None, diagonal: float = 1.0, method: str = "auto"):
+        if not isinstance(a, LinearElasticity):
+            raise TypeError("expected a femasm form descriptor (LinearElasticity, AsymDamage, ...)")
+        if method not in ("auto", "planned", "generic"):
+            raise ValueError(f"unknown method {method!r}: 'auto', 'planned' or 'generic'")
+        V = a.V
+        if V.family in ("DG", "Discontinuous Lagrange") or V.bs != V.mesh.gdim:
+            raise ValueError("the form's space must be a vector Lagrange space (bs = gdim)")
+        self.a, self.V = a, V
+        self.bcs = list(bcs or [])
+        self.diagonal = float(diagonal)
+        self.method = method
+        self.bs = V.bs
+        self._plan = None  # (buffer | None, chunks, bytes, cell visits), resolved on the first device use
+        if V.mesh.device.type == "cuda":
+            self._resolve()
+
+    @property
+    def shape(self):
+        return (self.V.num_dofs, self.V.num_dofs)
+
+    @staticmethod
+    def has_plan(V: FunctionSpace) -> bool:
+        """Whether V's element has a planned kernel (P1 / P2 triangles and tetrahedra)."""
+        return is_simplex(V.mesh.cell_type) and V.degree in (1, 2)
+
+    def _resolve(self):
+        if self._plan is not None:
+            return self._plan
+        V = self.V
+        generic = (None, 0, 0, V.mesh.num_cells * V.nn)
+        if self.method == "generic" or (self.method == "auto" and not self.has_plan(V)):
+            self._plan = generic
+            return self._plan
+        if not self.has_plan(V):
+            raise ValueError("method='planned': the planned kernel serves P1 / P2 triangles and tetrahedra only")
+        cached = V.__dict__.get("_apply_plan")
+        if cached is None:
+            L = _lib.load()
+            fm, adj = V._fa_mesh(), V._fa_adjacency()
+            sh = _lib.stream_handle(V.mesh.device)
+            nbytes, nch = ctypes.c_int64(0), ctypes.c_int64(0)
+            rc = L.fa_apply_plan_bytes(ctypes.byref(fm), ctypes.byref(adj), ctypes.byref(nbytes), ctypes.byref(nch), sh)
+            if rc == _lib.FA_OK:
+                buf = torch.empty(max(int(nbytes.value) // 8, 4), dtype=torch.int64, device=V.mesh.device)
+                rc = L.fa_apply_plan(ctypes.byref(fm), ctypes.byref(adj), buf.data_ptr(), buf.numel() * 8, sh)
+            if rc == _lib.FA_E_CAPACITY:
+                cached = ("capacity", L.fa_last_error().decode(errors="replace"))
+            else:
+                _lib.check(rc, "fa_apply_plan")
+                cached = (buf, int(nch.value), int(nbytes.value), int(buf[3]))
+            V.__dict__["_apply_plan"] = cached
+        if cached[0] == "capacity":
+            if self.method == "planned":
+                raise _lib.FemasmError(f"fa_apply_plan failed ({_lib.FA_E_CAPACITY}): {cached[1]}")
+            self._plan = generic
+        else:
+            self._plan = cached
+        return self._plan
+
+    @property
+    def num_chunks(self) -> int:
+        return self._resolve()[1]
+
+    @property
+    def plan_bytes(self) -> int:
+        return self._resolve()[2]
+
+    @property
+    def redundancy(self) -> float:
+        nc = self.V.mesh.num_cells
+        return self._resolve()[3] / nc if nc else 1.0
+
+    def _check_vector(self, t, name: str):
+        V = self.V
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float64:
+            raise ValueError(f"{name} must be a float64 tensor")
+        if t.dim() != 1 or t.numel() != V.num_dofs:
+            raise ValueError(f"{name} must have {V.num_dofs} entries (V.num_dofs), not {tuple(t.shape)}")
+        if not t.is_contiguous():
+            raise ValueError(f"{name} must be contiguous")
+        if t.device != V.mesh.device:
+            raise ValueError(f"{name} is on {t.device}, the mesh on {V.mesh.device}")
+
+    def mult(self, x: torch.Tensor, y: torch.Tensor | None = None) -> torch.Tensor:
+        """y = J(u) x for a dof vector x [num_dofs]; y (optional, not aliasing x) is overwritten. With y
+        given the call allocates no device memory."""
+        self._check_vector(x, "x")
+        if y is not None:
+            self._check_vector(y, "y")
+            n = 8 * x.numel()
+            if x.data_ptr() < y.data_ptr() + n and y.data_ptr() < x.data_ptr() + n:
+                raise ValueError("x and y must not alias")
+        else:
+            y = torch.empty_like(x)
+        V = self.V
+        plan = self._resolve()[0]
+        marker, _ = _combine_bcs(V, self.bcs, with_g=False)
+        fm, ff, adj = V._fa_mesh(), _fa_form(self.a), V._fa_adjacency()
+        _lib.check(_lib.load().fa_apply_jacobian(
+            ctypes.byref(fm), ctypes.byref(ff), ctypes.byref(adj), None if plan is None else plan.data_ptr(),
+            _lib.ptr(marker), self.diagonal, x.data_ptr(), y.data_ptr(), _lib.stream_handle(V.mesh.device)),
+            "fa_apply_jacobian")
+        return y
+
+    def block_diagonal(self) -> torch.Tensor:
+        """Diagonal blocks [num_nodes, bs, bs] of J(u) (the block-Jacobi preconditioner)."""
+        V = self.V
+        out = torch.empty((V.num_nodes, V.bs, V.bs), dtype=torch.float64, device=V.mesh.device)
+        marker, _ = _combine_bcs(V, self.bcs, with_g=False)
+        fm, ff, adj = V._fa_mesh(), _fa_form(self.a), V._fa_adjacency()
+        _lib.check(_lib.load().fa_jacobian_block_diag(
+            ctypes.byref(fm), ctypes.byref(ff), ctypes.byref(adj), _lib.ptr(marker), self.diagonal, out.data_ptr(),
+            _lib.stream_handle(V.mesh.device)), "fa_jacobian_block_diag")
+        return out
+
+
 class SplitGather:
     """fa_assemble_matrix(FA_GATHER) split into ``prepare()`` (per-cell records of all cells, once)
     and ``rows(i)`` (the rows of ``ranges[i]`` of one row part of A), via fa_gather_prepare /

@@ -13,7 +13,9 @@ C++: asym_elasto_damage_model.cc:705-714, 820-890) — with every operator on th
   F; residual0 = ||dx|| after the first update; convergence = the reference's own check
   (:870-890): ``||F|| / residual0 < rtol or ||F|| < atol``;
 * the Krylov solve is conjugate gradients on the assembled BSR matrix (``fa_bsr_mult``) with a
-  block-Jacobi preconditioner (``fa_bsr_block_diag``); ksp_rtol 1e-12 and max 2000 iterations as
+  block-Jacobi preconditioner (``fa_bsr_block_diag``), or, with ``NonlinearProblem(matrix_free=True)``,
+  on ``fem.JacobianOperator`` (``fa_apply_jacobian`` / ``fa_jacobian_block_diag``: no matrix is
+  assembled or stored); ksp_rtol 1e-12 and max 2000 iterations as
   the reference sets (:717). The reference preconditions with BoomerAMG (:720-813), which is out
   of scope here: iteration counts differ, the converged solution does not.
 
@@ -36,9 +38,11 @@ class NonlinearProblem:
     ``F`` and ``J`` are femasm forms (LinearElasticity / AsymDamage / NeoHookean) whose state
     ``u`` is this problem's ``u`` (the same storage: the driver updates it in place). ``J``
     defaults to ``F`` (the forms carry both the residual and its derivative).
+    ``matrix_free=True``: ``matrix()`` is a ``fem.JacobianOperator`` (diagonal 1, as ``J`` assembles)
+    that reads ``u`` live, and ``J`` does nothing: no matrix is assembled or stored.
     """
 
-    def __init__(self, F, u: fem.Function, bcs=None, J=None):
+    def __init__(self, F, u: fem.Function, bcs=None, J=None, matrix_free: bool = False):
         self.L = F
         self.a = J if J is not None else F
         self.u = u
@@ -46,6 +50,7 @@ class NonlinearProblem:
         for frm in (self.L, self.a):
             if frm.u is None or frm.u.data_ptr() != u.x.data_ptr():
                 raise ValueError("the forms' state u must be the problem's Function u (same storage)")
+        self.matrix_free = bool(matrix_free)
         self._A = None
 
     def form(self, x: torch.Tensor):
@@ -57,12 +62,15 @@ class NonlinearProblem:
         fem.apply_lifting(b, [self.a], [self.bcs], x0=[x], alpha=-1.0)
         fem.set_bc(b, self.bcs, x, -1.0)
 
-    def J(self, x: torch.Tensor, A: MatrixCSR):
+    def J(self, x: torch.Tensor, A: MatrixCSR | fem.JacobianOperator):
+        if self.matrix_free:
+            return  # the operator reads u live: nothing to assemble
         fem.assemble_matrix(self.a, bcs=self.bcs, diagonal=1.0, A=A)
 
-    def matrix(self) -> MatrixCSR:
+    def matrix(self) -> MatrixCSR | fem.JacobianOperator:
         if self._A is None:
-            self._A = fem.create_matrix(self.a)
+            self._A = fem.JacobianOperator(self.a, bcs=self.bcs, diagonal=1.0) if self.matrix_free \
+                else fem.create_matrix(self.a)
         return self._A
 
 
@@ -74,7 +82,8 @@ class KrylovSolver:
         self.rtol, self.atol, self.max_it = rtol, atol, max_it
         self.iterations = 0
 
-    def set_operator(self, A: MatrixCSR):
+    def set_operator(self, A: MatrixCSR | fem.JacobianOperator):
+        """A: anything with ``mult(x, y)``, ``block_diagonal()`` and ``bs``."""
         self.A = A
         D = A.block_diagonal()
         # rows without a diagonal block (none after assembly with bcs) keep identity

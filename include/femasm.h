@@ -350,6 +350,43 @@ int fa_bsr_mult(const fa_bsr* A, const double* x, double* y, void* stream);
  * the block-Jacobi preconditioner of the driver's CG (the reference uses BoomerAMG, :717-813). */
 int fa_bsr_block_diag(const fa_bsr* A, double* out, void* stream);
 
+/* Matrix-free Jacobian action (fa_version() >= 102): the Krylov solve of the Newton driver with no
+ * assembled matrix. The reference always assembles (MatSetValues into the PETSc matrix of
+ * FEniCSx/mechanic2d/asym_elasto_damage_model.cc:688, solved at :717-813); these calls replace the pair
+ * fa_assemble_matrix + fa_bsr_mult (and fa_bsr_block_diag) of that driver, not a reference interface.
+ *
+ * y = A x, where A is exactly the matrix fa_assemble_matrix(mesh, form, ..., bc, diag, ...) would hold,
+ * evaluated at the form's current state form->u. Free row i: sum over free columns j of A_ij x_j (cell
+ * contributions only). Constrained row i (bc[i] != 0): y_i = diag * x_i. Constrained columns contribute
+ * nothing. y is overwritten (every dof written exactly once), not added into. x and y must not alias
+ * (FA_E_ARG). `plan`: an apply plan (below) or NULL = the generic node-parallel kernel (every supported
+ * cell, degree and form kind, affine or not). Deterministic: no atomics, bit-identical run to run. No
+ * allocation, no synchronisation (the element tables are cached on the first call per element, as
+ * everywhere). A plan must be the one built for this mesh and adjacency: the kernel checks its header
+ * on the device and writes nothing when it does not match. */
+int fa_apply_jacobian(const fa_mesh* mesh, const fa_form* form, const fa_adjacency* adj, const void* plan,
+                      const int8_t* bc /* or NULL */, double diag, const double* x, double* y, void* stream);
+
+/* out[a] = the diagonal block (a, a) of that same A, [nnodes][bs][bs] (zeroed bc rows / columns inside
+ * the block, `diag` on constrained diagonal entries): the block-Jacobi preconditioner with no matrix.
+ * Node-parallel through the adjacency, every supported element and form kind; bc may be NULL. */
+int fa_jacobian_block_diag(const fa_mesh* mesh, const fa_form* form, const fa_adjacency* adj, const int8_t* bc,
+                           double diag, double* out, void* stream);
+
+/* Apply plan of the planned kernel (P1 / P2 triangles and tetrahedra, every form kind defined on them;
+ * other elements: FA_E_UNSUPPORTED, use plan = NULL): a caller-owned, 8-byte aligned device buffer, built
+ * once per (mesh, space), in the style of fa_plan_contrib_bytes / fa_plan_contrib. The rows are cut into
+ * chunks of consecutive nodes whose distinct cells fit a 256-cell LDS tile; the buffer holds each chunk's
+ * cell list and, per adjacency entry, the tile position of its (cell, local node) result: at most 6 bytes
+ * per dofmap entry (ncells * nn) + 16 per chunk + 64. One workgroup per chunk then computes every
+ * distinct cell's K_e(u) x_e once and sums the rows from the tile. Both calls synchronise `stream`
+ * (_bytes to return the size; *nchunks may be NULL). A node with more cells than the tile holds:
+ * FA_E_CAPACITY with the sizes in fa_last_error() (the caller then uses the generic kernel). Words 1 and 3
+ * of the buffer's int64 header are the chunk count and the cell visits per launch (their ratio to ncells
+ * is the redundancy left: 1 when no cell straddles chunks). */
+int fa_apply_plan_bytes(const fa_mesh* mesh, const fa_adjacency* adj, int64_t* bytes, int64_t* nchunks, void* stream);
+int fa_apply_plan(const fa_mesh* mesh, const fa_adjacency* adj, void* buf, int64_t bytes, void* stream);
+
 /* Measurement helper (not part of the reference interface): a 16-B-per-lane grid-stride stream
  * over n doubles (n even, 16-B aligned buffers) for the measured HBM peak beside the 8 TB/s spec
  * (SURVEY.md section 8(d)). mode 0: dst = src (copy), 1: dst = 1.0 (write only), 2: read src
