@@ -8,14 +8,14 @@
 // used here, not copied.
 //
 // fa_version is this file's (101: fa_eval_cells present; 102: the matrix-free Jacobian action of
-// femasm_apply.hip, included at the end of this file); femasm.hip's own definition is compiled under
-// another, hidden name.
+// femasm_apply.hip, included at the end of this file; 103: the multigrid transfers and smoother step of
+// femasm_mg.hip, included after it); femasm.hip's own definition is compiled under another, hidden name.
 #include "../../include/femasm.h"
 #define fa_version __attribute__((visibility("hidden"))) fa_version_assembly
 #include "femasm.hip"
 #undef fa_version
 
-extern "C" int fa_version(void) { return 102; }
+extern "C" int fa_version(void) { return 103; }
 
 // ------------------------------------------------------------------------------------ expressions
 constexpr int EV_LIN = 0, EV_DAMAGE = 1, EV_NEO = 2;
@@ -335,3 +335,6 @@ extern "C" int fa_eval_cells(const fa_mesh* mesh, const fa_form* form, int32_t n
 
 // ------------------------------------------------------------------------------------ matrix-free Jacobian action
 #include "femasm_apply.hip"
+
+// ------------------------------------------------------------------------------------ geometric multigrid
+#include "femasm_mg.hip"

@@ -90,6 +90,16 @@ class fa_plan(ctypes.Structure):
     ]
 
 
+class fa_transfer(ctypes.Structure):
+    _fields_ = [
+        ("tdim", ctypes.c_int32),
+        ("simplex", ctypes.c_int32),
+        ("bs", ctypes.c_int32),
+        ("_pad", ctypes.c_int32),
+        ("nc", ctypes.c_int64 * 3),
+    ]
+
+
 # exported symbols with their signatures; tests check every one against include/femasm.h
 P = ctypes.c_void_p
 I32, I64, D = ctypes.c_int32, ctypes.c_int64, ctypes.c_double
@@ -127,6 +137,9 @@ SIGNATURES = {
     "fa_jacobian_block_diag": (ctypes.c_int, [P, P, P, P, D, P, P]),
     "fa_apply_plan_bytes": (ctypes.c_int, [P, P, P, P, P]),
     "fa_apply_plan": (ctypes.c_int, [P, P, P, I64, P]),
+    "fa_prolong": (ctypes.c_int, [P, P, P, P, I32, P, P]),
+    "fa_restrict": (ctypes.c_int, [P, P, P, P, P, P]),
+    "fa_cheb_step": (ctypes.c_int, [I64, I32, P, P, P, D, D, P, P, P]),
     "fa_hbm_probe": (ctypes.c_int, [I32, P, P, I64, P]),
 }
 

@@ -1,0 +1,523 @@
+"""Geometric multigrid preconditioner for the Newton-Krylov solve on the structured meshes.
+
+The reference preconditions its Krylov solve with BoomerAMG (FEniCSx/mechanic2d/asym_elasto_damage_model.cc:720-813,
+MFEM/mechanic2d/asym_elasto_damage_model.cc:1502-1528); ``nls.KrylovSolver`` alone has block-Jacobi, whose
+iteration count grows like 1/h. ``GeometricMultigrid`` needs no assembled fine matrix: level 0 is the
+matrix-free ``fem.JacobianOperator`` (or any operator with ``mult`` / ``block_diagonal``), the coarser
+levels are rediscretised and assembled (a degree-1 level is at most 1/8 of the fine dofs).
+
+One stencil serves every transfer. With the lattice node numbering of the structured meshes the degree-2
+nodes of an ``n`` mesh and the degree-1 nodes of a ``2n`` mesh are the same lattice, and the right-diagonal
+triangle / Kuhn tetrahedron mesh of ``2n`` refines that of ``n``; so linear interpolation between a coarse
+lattice of ``nc + 1`` points per axis and the fine lattice of ``2 nc + 1`` points is both the P2 -> P1
+transfer on one mesh (p-coarsening) and the P1(h) -> P1(2h) transfer (h-coarsening). A fine point ``I``
+with odd mask ``o = I & 1`` takes, on simplices, half of each of the coarse points ``(I - o) / 2`` and
+``(I + o) / 2`` (``o`` is always an edge direction of the mesh), and on tensor cells the mean of the
+``2^|o|`` coarse points ``(I +- o) / 2``. ``fa_prolong`` / ``fa_restrict`` apply it (gathers, no atomics)
+and ``fa_cheb_step`` is the fused Chebyshev / block-Jacobi smoother update (femasm_mg.hip).
+"""
+from __future__ import annotations
+
+import ctypes
+import itertools
+from dataclasses import dataclass
+
+import numpy as np
+import torch
+
+from . import _lib, fem
+from . import mesh as fmesh
+from .mesh import CellType
+
+# Chebyshev interval as fractions of the estimated largest eigenvalue of D^-1 A (PETSc's defaults for
+# PCMG's Chebyshev smoother) and the steps of the eigenvalue estimate
+CHEB_LOWER, CHEB_UPPER = 0.1, 1.1
+EIG_STEPS = 10
+COARSE_CHEB_DEGREE = 8  # the fixed polynomial standing in for a solve on a coarsest level too large to factor
+
+# local cube vertices (v = i + 2 j + 4 k) of the sub-simplices of a lattice square / cube, in the cell
+# order of mesh.create_rectangle(diagonal="right") and mesh.create_box
+_SUB_SIMPLICES = {CellType.triangle: ((0, 1, 3), (0, 2, 3)), CellType.tetrahedron: fmesh.KUHN_TETS}
+
+
+@dataclass(frozen=True)
+class Transfer:
+    """Coarse lattice of ``nc[d] + 1`` points per axis <-> fine lattice of ``2 nc[d] + 1`` points
+    (fa_transfer); dof = node * bs + comp."""
+    tdim: int
+    simplex: bool
+    bs: int
+    nc: tuple
+
+    @property
+    def coarse_points(self) -> tuple:
+        return tuple(int(k) + 1 for k in self.nc)
+
+    @property
+    def fine_points(self) -> tuple:
+        return tuple(2 * int(k) + 1 for k in self.nc)
+
+    @property
+    def num_coarse_dofs(self) -> int:
+        return int(np.prod(self.coarse_points)) * self.bs
+
+    @property
+    def num_fine_dofs(self) -> int:
+        return int(np.prod(self.fine_points)) * self.bs
+
+    def _fa(self) -> _lib.fa_transfer:
+        t = _lib.fa_transfer()
+        t.tdim, t.simplex, t.bs = self.tdim, int(self.simplex), self.bs
+        for d in range(3):
+            t.nc[d] = int(self.nc[d]) if d < self.tdim else 0
+        return t
+
+
+def _lattice_index(points, dims):
+    """Node index of lattice points [..., tdim] (index 0 fastest)."""
+    idx = points[..., len(dims) - 1]
+    for d in range(len(dims) - 2, -1, -1):
+        idx = idx * dims[d] + points[..., d]
+    return idx
+
+
+def transfer_matrix(t: Transfer):
+    """The prolongation P [fine dofs, coarse dofs] of ``t`` as a scipy CSR matrix (host; tests and
+    debugging): ``P[i_f, i_c]`` = the coarse P1 / Q1 basis function ``i_c`` at fine node ``i_f``."""
+    import scipy.sparse as sp
+
+    pf, pc = t.fine_points, t.coarse_points
+    grids = np.meshgrid(*[np.arange(k) for k in reversed(pf)], indexing="ij")
+    I = np.stack([g.reshape(-1) for g in reversed(grids)], 1)  # [nf, tdim], index 0 fastest
+    o = I & 1
+    a = (I - o) // 2
+    nf = I.shape[0]
+    rows, cols, vals = [], [], []
+    # each odd axis splits the weight over its two coarse neighbours; an even axis sends both halves to
+    # the same point (duplicates are summed). Simplices move along the whole vector o at once.
+    combos = [(0,) * t.tdim, (1,) * t.tdim] if t.simplex else list(itertools.product((0, 1), repeat=t.tdim))
+    for s in combos:
+        rows.append(np.arange(nf))
+        cols.append(_lattice_index(a + np.array(s) * o, pc))
+        vals.append(np.full(nf, 1.0 / len(combos)))
+    P = sp.coo_matrix((np.concatenate(vals), (np.concatenate(rows), np.concatenate(cols))),
+                      shape=(nf, int(np.prod(pc)))).tocsr()
+    P.sum_duplicates()
+    return sp.kron(P, sp.identity(t.bs), format="csr") if t.bs > 1 else P
+
+
+def injection_nodes(t: Transfer, device=None) -> torch.Tensor:
+    """Fine node index of every coarse node (coarse point I coincides with fine point 2 I), int64."""
+    pc, pf = t.coarse_points, t.fine_points
+    axes = [torch.arange(k, device=device, dtype=torch.int64) for k in reversed(pc)]
+    grids = torch.meshgrid(*axes, indexing="ij")
+    I = torch.stack([g.reshape(-1) for g in reversed(grids)], 1)
+    return _lattice_index(2 * I, pf)
+
+
+def coarsen_marker(marker: torch.Tensor | None, t: Transfer) -> torch.Tensor | None:
+    """Constraint marker of the coarse level: a coarse node is constrained in the components in which
+    its coinciding fine node is."""
+    if marker is None:
+        return None
+    return marker.view(-1, t.bs)[injection_nodes(t, marker.device)].reshape(-1).contiguous()
+
+
+def parent_cells(cell_type, nc, device=None) -> torch.Tensor:
+    """Parent (coarse) cell of every cell of the structured ``2 nc`` mesh in the ``nc`` mesh, int64
+    [fine cells], with the cell numbering of mesh.create_rectangle(diagonal="right") / create_box. The
+    fine cell's centroid in coarse lattice units gives the coarse square / cube (floor) and, on
+    simplices, the sub-simplex (the order of its local coordinates)."""
+    ct = CellType(cell_type)
+    nc = tuple(int(k) for k in nc)
+    tdim = len(nc)
+    subs = _SUB_SIMPLICES.get(ct)
+    m = len(subs) if subs else 1
+    nf = tuple(2 * k for k in nc)
+    axes = [torch.arange(k, device=device, dtype=torch.int64) for k in reversed(nf)]
+    grids = torch.meshgrid(*axes, indexing="ij")
+    sq = torch.stack([g.reshape(-1) for g in reversed(grids)], 1)  # fine squares, index 0 fastest
+    csq = _lattice_index(torch.div(sq, 2, rounding_mode="floor"), nc)  # coarse square of each fine one
+    if subs is None:
+        return csq
+    bits = lambda v: [(v >> d) & 1 for d in range(tdim)]
+    # centroid of each fine sub-simplex in fine lattice units, relative to its square
+    cref = torch.tensor([[sum(bits(v)[d] for v in s) / len(s) for d in range(tdim)] for s in subs],
+                        dtype=torch.float64, device=device)
+    xi = (sq[:, None, :].to(torch.float64) + cref[None, :, :]) / 2.0
+    xi = xi - torch.floor(xi)  # local coordinates in the coarse square [nsq, m, tdim]
+    # sub-simplex s is the region xi[a1] >= xi[a2] (>= xi[a3]), a_k = the axis its k-th edge of the path
+    # from vertex 0 to the far corner runs along; key = the axes in descending order of xi
+    table = torch.zeros(tdim ** tdim, dtype=torch.int64, device=device)
+    for s, verts in enumerate(subs):
+        path = sorted(verts, key=lambda v: bin(v).count("1"))
+        order = [(path[k + 1] ^ path[k]).bit_length() - 1 for k in range(tdim)]
+        table[sum(a * tdim ** (tdim - 1 - k) for k, a in enumerate(order))] = s
+    order = torch.argsort(xi, dim=-1, descending=True, stable=True)
+    key = sum(order[..., k] * tdim ** (tdim - 1 - k) for k in range(tdim))
+    return (csq[:, None] * m + table[key]).reshape(-1)
+
+
+def plan_hierarchy(V: fem.FunctionSpace, coarse_dofs: int = 6000, max_levels: int | None = None) -> list:
+    """Level table [(degree, n), ...] of a space on a structured mesh: the space itself, degree 1 on the
+    same mesh if it has degree 2, then every ``n`` halved while all are even and >= 2, until a level has
+    at most ``coarse_dofs`` dofs or ``max_levels`` levels exist. ValueError for the spaces geometric
+    multigrid cannot serve."""
+    m = V.mesh
+    st = m.structured
+    if st is None:
+        raise ValueError("GeometricMultigrid needs a structured mesh (mesh.create_rectangle / create_box): "
+                         "unstructured meshes have no lattice to coarsen")
+    n = tuple(int(k) for k in st["n"])
+    if st.get("z_range") is not None and tuple(st["z_range"]) != (0, n[-1]):
+        raise ValueError(f"GeometricMultigrid needs the whole box, not the z_range={tuple(st['z_range'])} slab")
+    if m.cell_type == CellType.triangle and st.get("diagonal", "right") != "right":
+        raise ValueError("GeometricMultigrid needs diagonal='right' triangles: the 'left' mesh of 2n does not "
+                         "refine that of n along the lattice stencil")
+    if V.family in ("DG", "Discontinuous Lagrange") or V.degree not in (1, 2):
+        raise ValueError(f"GeometricMultigrid serves Lagrange degree 1 and 2, not {V.family} degree {V.degree} "
+                         "(the degree-3 GLL nodes are not nested in a finer lattice)")
+    if max_levels is not None and max_levels < 1:
+        raise ValueError("max_levels must be at least 1")
+    ndofs = lambda p, k: int(np.prod([p * j + 1 for j in k])) * V.bs
+    levels = [(V.degree, n)]
+    while (max_levels is None or len(levels) < max_levels) and ndofs(*levels[-1]) > coarse_dofs:
+        p, k = levels[-1]
+        if p == 2:
+            levels.append((1, k))
+        elif all(j % 2 == 0 and j >= 2 for j in k):
+            levels.append((1, tuple(j // 2 for j in k)))
+        else:
+            break
+    if len(levels) == 1 and (max_levels is None or max_levels > 1) and ndofs(*levels[0]) > coarse_dofs:
+        raise ValueError(f"a degree-1 space on n={n} has no coarser level (every n must be even and >= 2) and "
+                         f"its {ndofs(1, n)} dofs exceed coarse_dofs={coarse_dofs}")
+    return levels
+
+
+class _Level:
+    pass
+
+
+def _transfer_call(name, t: Transfer, *args):
+    fa = t._fa()
+    _lib.check(getattr(_lib.load(), name)(ctypes.byref(fa), *args), name)
+
+
+def prolong(t: Transfer, xc: torch.Tensor, xf: torch.Tensor, bc_c=None, bc_f=None, add: bool = False) -> torch.Tensor:
+    """xf (+)= M_f P M_c xc (fa_prolong); markers int8 per dof or None."""
+    _check_transfer_args(t, xc, xf, bc_c, bc_f)
+    _transfer_call("fa_prolong", t, xc.data_ptr(), _lib.ptr(bc_c), _lib.ptr(bc_f), int(bool(add)), xf.data_ptr(),
+                   _lib.stream_handle(xf.device))
+    return xf
+
+
+def restrict(t: Transfer, rf: torch.Tensor, rc: torch.Tensor, bc_f=None, bc_c=None) -> torch.Tensor:
+    """rc = M_c P^T M_f rf (fa_restrict); bit-reproducible."""
+    _check_transfer_args(t, rc, rf, bc_c, bc_f)
+    _transfer_call("fa_restrict", t, rf.data_ptr(), _lib.ptr(bc_f), _lib.ptr(bc_c), rc.data_ptr(),
+                   _lib.stream_handle(rc.device))
+    return rc
+
+
+def _check_transfer_args(t, c, f, bc_c, bc_f):
+    for name, v, n, dt in (("coarse vector", c, t.num_coarse_dofs, torch.float64),
+                           ("fine vector", f, t.num_fine_dofs, torch.float64),
+                           ("coarse marker", bc_c, t.num_coarse_dofs, torch.int8),
+                           ("fine marker", bc_f, t.num_fine_dofs, torch.int8)):
+        if v is None and "marker" in name:
+            continue
+        if not isinstance(v, torch.Tensor) or v.dtype != dt or v.numel() != n or not v.is_contiguous():
+            raise ValueError(f"the {name} must be a contiguous {dt} tensor of {n} entries")
+        if v.device != f.device:
+            raise ValueError(f"the {name} is on {v.device}, the fine vector on {f.device}")
+
+
+def cheb_step(Dinv: torch.Tensor, b: torch.Tensor, Ax: torch.Tensor | None, c_d: float, c_r: float,
+              d: torch.Tensor, x: torch.Tensor):
+    """d <- c_d d + c_r Dinv (b - Ax), x <- x + d in one pass (fa_cheb_step). Dinv [nnodes, bs, bs];
+    Ax None: A x = 0."""
+    nn, bs = int(Dinv.shape[0]), int(Dinv.shape[1])
+    for v in (b, Ax, d, x):
+        if v is not None and (v.dtype != torch.float64 or v.numel() != nn * bs or not v.is_contiguous()
+                              or v.device != Dinv.device):
+            raise ValueError(f"fa_cheb_step vectors must be contiguous float64 of {nn * bs} entries on {Dinv.device}")
+    if Dinv.dtype != torch.float64 or not Dinv.is_contiguous() or Dinv.shape[2] != bs:
+        raise ValueError("Dinv must be a contiguous float64 [nnodes, bs, bs] tensor")
+    _lib.check(_lib.load().fa_cheb_step(nn, bs, Dinv.data_ptr(), b.data_ptr(), _lib.ptr(Ax), float(c_d), float(c_r),
+                                        d.data_ptr(), x.data_ptr(), _lib.stream_handle(x.device)), "fa_cheb_step")
+
+
+def chebyshev_coefficients(lo: float, hi: float, degree: int) -> list:
+    """(c_d, c_r) of each step of the Chebyshev iteration on [lo, hi] (Saad, Iterative Methods, alg. 12.1)."""
+    theta, delta = 0.5 * (hi + lo), 0.5 * (hi - lo)
+    sigma = theta / delta
+    rho = 1.0 / sigma
+    out = [(0.0, 1.0 / theta)]
+    for _ in range(1, degree):
+        rho_new = 1.0 / (2.0 * sigma - rho)
+        out.append((rho_new * rho, 2.0 * rho_new / delta))
+        rho = rho_new
+    return out
+
+
+class GeometricMultigrid:
+    """One V-cycle of geometric multigrid as a fixed, symmetric positive definite preconditioner
+    (``apply(r, z)`` / ``update()``: the interface of ``nls.KrylovSolver.set_preconditioner``).
+
+    a: the Jacobian form on a structured mesh (LinearElasticity / AsymDamage / NeoHookean); bcs, diagonal
+    as ``fem.assemble_matrix``. Level 0 is the form's own space with ``fine_operator`` (anything with
+    ``mult(x, y)`` and ``block_diagonal()``) or ``fem.JacobianOperator(a, bcs, diagonal)``; a degree-2
+    space is followed by degree 1 on the same mesh; further levels halve every ``n`` (``plan_hierarchy``).
+    Coarse forms are rediscretised with the same form class: per-cell coefficients are the mean over the
+    child cells, the nodal state is injected, a coarse node is constrained where its coinciding fine node
+    is; coarse operators are assembled (``fem.assemble_matrix``). The smoother is Chebyshev of degree
+    ``smoother_degree`` over block-Jacobi on [0.1, 1.1] x the estimated largest eigenvalue of D^-1 A,
+    the same polynomial before and after the coarse correction. A coarsest level of at most
+    ``coarse_dofs`` dofs is inverted densely at ``update()``, a larger one gets a fixed Chebyshev
+    polynomial of degree 8.
+
+    ``update()`` must follow every change of the state (``KrylovSolver.set_operator`` calls it); the
+    first ``apply`` runs it if nobody has. ``levels``: [(degree, n, num_dofs, kind)];
+    ``operator_complexity``: stored matrix entries of all levels over those of the level-0 matrix."""
+
+    def __init__(self, a, bcs=None, diagonal: float = 1.0, fine_operator=None, smoother_degree: int = 2,
+                 coarse_dofs: int = 6000, max_levels: int | None = None):
+        if not isinstance(a, fem.LinearElasticity):
+            raise TypeError("expected a femasm form descriptor (LinearElasticity, AsymDamage, ...)")
+        if smoother_degree < 1:
+            raise ValueError("smoother_degree must be at least 1")
+        V = a.V
+        table = plan_hierarchy(V, coarse_dofs, max_levels)
+        if V.bs != V.mesh.gdim:
+            raise ValueError("the form's space must be a vector Lagrange space (bs = gdim)")
+        self.a, self.V = a, V
+        self.bcs = list(bcs or [])
+        self.diagonal = float(diagonal)
+        self.smoother_degree = int(smoother_degree)
+        self.coarse_dofs = int(coarse_dofs)
+        self.updates = 0
+        m, dev, bs = V.mesh, V.mesh.device, V.bs
+        simplex = fem.is_simplex(m.cell_type)
+        st = m.structured
+        self._levels = []
+        for li, (p, n) in enumerate(table):
+            L = _Level()
+            L.degree, L.n = p, n
+            if li == 0:
+                L.V, L.a = V, a
+                L.marker, _ = fem._combine_bcs(V, self.bcs, with_g=False)
+                L.A = fine_operator if fine_operator is not None else \
+                    fem.JacobianOperator(a, bcs=self.bcs, diagonal=self.diagonal)
+                L.kind = "matrix-free" if isinstance(L.A, fem.JacobianOperator) else "operator"
+            else:
+                F = self._levels[-1]
+                if n == F.n:
+                    cm = F.V.mesh
+                elif m.tdim == 2:
+                    cm = fmesh.create_rectangle(st["lengths"], n, m.cell_type, st.get("diagonal", "right"), dev)
+                else:
+                    cm = fmesh.create_box(st["lengths"], n, m.cell_type, dev)
+                L.V = fem.functionspace(cm, ("Lagrange", 1, (bs,)))
+                F.transfer = Transfer(m.tdim, simplex, bs, n)
+                F.inject = injection_nodes(F.transfer, dev)
+                F.parents = None if n == F.n else parent_cells(m.cell_type, n, dev)
+                L.marker = coarsen_marker(F.marker, F.transfer)
+                self._coarse_form(F, L)
+                L.A = fem.create_matrix(L.a)
+                L.kind = "assembled"
+            L.transfer = None
+            nd = L.V.num_dofs
+            L.r, L.z, L.d, L.t = (torch.zeros(nd, dtype=torch.float64, device=dev) for _ in range(4))
+            L.Dinv = L.coef = L.Ainv = None
+            self._levels.append(L)
+        last = self._levels[-1]
+        last.direct = last.V.num_dofs <= self.coarse_dofs
+        if len(self._levels) > 1 or last.direct:
+            last.kind = "direct" if last.direct else "chebyshev"
+        mk = self._levels[0].marker
+        self._free = None if mk is None else (mk == 0).to(torch.float64)
+        # z = r / diagonal on the constrained dofs, + 0 (r / inf) on the free ones
+        self._cdiv = None if mk is None else torch.where(mk != 0, self.diagonal, float("inf")).to(torch.float64)
+        self._gen = torch.Generator(device=dev)
+        self._nnz0 = None
+
+    # ------------------------------------------------------------------------------ hierarchy
+    def _coarse_form(self, F, L):
+        """Rediscretise F.a on L.V with storage of its own for the coefficients and the state
+        (update() refills it in place)."""
+        a, t = F.a, F.transfer
+        dev = L.V.mesh.device
+        nc = L.V.mesh.num_cells
+        same = F.parents is None
+        L.cell = {}
+        for k in ("E", "lam", "mu"):
+            v = getattr(a, k)
+            if v is not None:
+                L.cell[k] = v if same else torch.empty(nc, dtype=torch.float64, device=dev)
+        L.u = None if a.u is None else torch.zeros(t.num_coarse_dofs, dtype=torch.float64, device=dev)
+        L.dmg = None if a.d is None else torch.zeros(t.num_coarse_dofs // t.bs, dtype=torch.float64, device=dev)
+        kw = dict(nu=a.nu, u=L.u, **L.cell)
+        if isinstance(a, fem.AsymDamage):
+            L.a = fem.AsymDamage(L.V, d=L.dmg, tangent=a.tangent, **kw)
+        elif isinstance(a, fem.NeoHookean):
+            L.a = fem.NeoHookean(L.V, **kw)
+        else:
+            L.a = fem.LinearElasticity(L.V, **kw)
+        if L.marker is not None and bool(L.marker.any()):
+            dofs = torch.nonzero(L.marker, as_tuple=False).reshape(-1)
+            L.bcs = [fem.DirichletBC(L.V, dofs, torch.zeros(L.V.num_dofs, dtype=torch.float64, device=dev))]
+        else:
+            L.bcs = None
+
+    def _refill(self, F, L):
+        """Coefficients (mean over the children) and state (injection) of level L from level F."""
+        if F.parents is not None:
+            children = float(2 ** self.V.mesh.tdim)
+            for k, vc in L.cell.items():
+                vc.zero_().index_add_(0, F.parents, getattr(F.a, k)).div_(children)
+        bs = F.transfer.bs
+        if L.u is not None:
+            L.u.copy_(F.a.u.view(-1, bs)[F.inject].reshape(-1))
+        if L.dmg is not None:
+            L.dmg.copy_(F.a.d[F.inject])
+
+    @property
+    def levels(self) -> list:
+        return [(L.degree, L.n, L.V.num_dofs, L.kind) for L in self._levels]
+
+    @property
+    def operator_complexity(self) -> float:
+        """Matrix entries of all levels (the level-0 matrix counted as if assembled) over those of the
+        level-0 matrix. Builds level 0's sparsity pattern on first use when that level is matrix-free."""
+        if self._nnz0 is None:
+            A0 = self._levels[0].A
+            self._nnz0 = A0.nnz if hasattr(A0, "nnz") else \
+                int(fem.sparsity_pattern(self.V)[1].numel()) * self.V.bs ** 2
+        return (self._nnz0 + sum(L.A.nnz for L in self._levels[1:])) / self._nnz0
+
+    # ------------------------------------------------------------------------------ setup
+    def _estimate_lmax(self, L) -> float:
+        """Largest eigenvalue of D^-1 A from EIG_STEPS steps of block-Jacobi CG on a seeded right-hand
+        side (the Lanczos tridiagonal of the CG coefficients); deterministic."""
+        bs = L.V.bs
+        r, z, p, Ap = L.r, L.z, L.d, L.t
+        self._gen.manual_seed(1234)
+        r.uniform_(-1.0, 1.0, generator=self._gen)
+        if L.marker is not None:
+            r.mul_(L.marker == 0)
+        prec = lambda v, out: torch.bmm(L.Dinv, v.view(-1, bs, 1), out=out.view(-1, bs, 1))
+        prec(r, z)
+        p.copy_(z)
+        rz = torch.dot(r, z)
+        alphas, betas = [], []
+        for _ in range(EIG_STEPS):
+            L.A.mult(p, Ap)
+            alpha = rz / torch.dot(p, Ap)
+            r.sub_(alpha * Ap)
+            prec(r, z)
+            rz_new = torch.dot(r, z)
+            beta = rz_new / rz
+            p.mul_(beta).add_(z)
+            rz = rz_new
+            alphas.append(alpha)
+            betas.append(beta)
+        al, be = torch.stack(alphas).cpu().numpy(), torch.stack(betas).cpu().numpy()
+        k = 0  # steps before a breakdown (an exact solve on a tiny level)
+        while k < EIG_STEPS and np.isfinite(al[k]) and al[k] > 0 and (k == 0 or (np.isfinite(be[k - 1]) and be[k - 1] > 0)):
+            k += 1
+        if k == 0:
+            raise RuntimeError("eigenvalue estimate broke down: is the operator symmetric positive definite?")
+        T = np.zeros((k, k))
+        for j in range(k):
+            T[j, j] = 1.0 / al[j] + (be[j - 1] / al[j - 1] if j else 0.0)
+            if j + 1 < k:
+                T[j, j + 1] = T[j + 1, j] = np.sqrt(be[j]) / al[j]
+        for v in (r, z, p, Ap):
+            v.zero_()
+        return float(np.linalg.eigvalsh(T)[-1])
+
+    def update(self):
+        """Re-inject the state, re-assemble the coarse matrices and refresh each level's block-Jacobi
+        inverse, eigenvalue estimate and the coarsest level's dense inverse."""
+        Ls = self._levels
+        for F, L in zip(Ls[:-1], Ls[1:]):
+            self._refill(F, L)
+            fem.assemble_matrix(L.a, bcs=L.bcs, diagonal=self.diagonal, A=L.A)
+        for L in Ls:
+            last = L is Ls[-1]
+            if last and L.direct:
+                L.Ainv = self._dense_inverse(L)
+                continue
+            D = L.A.block_diagonal()
+            bad = D.abs().sum((1, 2)) == 0  # rows without a diagonal block keep identity (as KrylovSolver)
+            D[bad] = torch.eye(L.V.bs, dtype=D.dtype, device=D.device)
+            L.Dinv = torch.linalg.inv(D).contiguous()
+            L.lmax = self._estimate_lmax(L)
+            degree = COARSE_CHEB_DEGREE if last else self.smoother_degree
+            L.coef = chebyshev_coefficients(CHEB_LOWER * L.lmax, CHEB_UPPER * L.lmax, degree)
+        self.updates += 1
+
+    def _dense_inverse(self, L) -> torch.Tensor:
+        A = L.A
+        if not hasattr(A, "indptr"):  # a single matrix-free level: probe it with the identity
+            n = L.V.num_dofs
+            eye = torch.eye(n, dtype=torch.float64, device=L.r.device)
+            M = torch.stack([A.mult(eye[j].contiguous()) for j in range(n)], 1)
+        else:
+            nb, bs = A.num_block_rows, A.bs
+            rows = torch.repeat_interleave(torch.arange(nb, device=A.indices.device), A.indptr[1:] - A.indptr[:-1])
+            M = torch.zeros((nb, bs, nb, bs), dtype=torch.float64, device=A.indices.device)
+            M[rows, :, A.indices.to(torch.int64), :] = A.data
+            M = M.reshape(nb * bs, nb * bs)
+        Minv = torch.linalg.inv(M)
+        return (0.5 * (Minv + Minv.T)).contiguous()
+
+    # ------------------------------------------------------------------------------ cycle
+    def _smooth(self, L, zero_guess: bool):
+        """z <- z + p(D^-1 A) D^-1 (r - A z), the level's Chebyshev polynomial (z = 0 on entry when
+        zero_guess: the first residual is r itself)."""
+        for k, (cd, cr) in enumerate(L.coef):
+            if k == 0 and zero_guess:
+                L.z.zero_()
+                Ax = None
+            else:
+                Ax = L.A.mult(L.z, L.t)
+            cheb_step(L.Dinv, L.r, Ax, cd, cr, L.d, L.z)
+
+    def _cycle(self, li: int):
+        L = self._levels[li]
+        if li == len(self._levels) - 1:
+            if L.direct:
+                L.z.addmv_(L.Ainv, L.r, beta=0.0)  # (torch.mv(out=...) allocates a temporary)
+            else:
+                self._smooth(L, True)
+            return
+        C = self._levels[li + 1]
+        self._smooth(L, True)
+        L.A.mult(L.z, L.t)
+        torch.sub(L.r, L.t, out=L.t)
+        restrict(L.transfer, L.t, C.r, bc_f=L.marker, bc_c=C.marker)
+        self._cycle(li + 1)
+        prolong(L.transfer, C.z, L.z, bc_c=C.marker, bc_f=L.marker, add=True)
+        self._smooth(L, False)
+
+    def apply(self, r: torch.Tensor, z: torch.Tensor | None = None) -> torch.Tensor:
+        """z = M r: one V-cycle on the free dofs, z = r / diagonal on the constrained ones (they are
+        decoupled from the rest, so M stays symmetric positive definite). With z given the call
+        allocates nothing."""
+        if self.updates == 0:
+            self.update()
+        L0 = self._levels[0]
+        if z is None:
+            z = torch.empty_like(r)
+        if self._free is None:
+            L0.r.copy_(r)
+        else:
+            torch.mul(r, self._free, out=L0.r)
+        self._cycle(0)
+        if self._free is None:
+            z.copy_(L0.z)
+        else:
+            torch.addcdiv(L0.z, r, self._cdiv, out=z)
+        return z

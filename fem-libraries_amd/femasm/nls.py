@@ -18,6 +18,9 @@ C++: asym_elasto_damage_model.cc:705-714, 820-890) — with every operator on th
   assembled or stored); ksp_rtol 1e-12 and max 2000 iterations as
   the reference sets (:717). The reference preconditions with BoomerAMG (:720-813), which is out
   of scope here: iteration counts differ, the converged solution does not.
+  ``KrylovSolver.set_preconditioner(mg.GeometricMultigrid(J, bcs))`` replaces block-Jacobi with a
+  geometric multigrid V-cycle on the structured meshes (femasm.mg), whose iteration count does not
+  grow like 1/h.
 
 Single GPU (the assembly's multi-GPU path is ``femasm.parallel``; a distributed Krylov solve is
 not part of this module).
@@ -81,10 +84,21 @@ class KrylovSolver:
     def __init__(self, rtol: float = 1e-12, atol: float = 1e-50, max_it: int = 2000):
         self.rtol, self.atol, self.max_it = rtol, atol, max_it
         self.iterations = 0
+        self.M = None
+
+    def set_preconditioner(self, M):
+        """M: anything with ``apply(r, z)`` (z = M r, a fixed symmetric positive definite operator) and
+        ``update()`` (called by every ``set_operator``), e.g. ``mg.GeometricMultigrid``; None restores
+        block-Jacobi."""
+        self.M = M
+        self._z = None
 
     def set_operator(self, A: MatrixCSR | fem.JacobianOperator):
         """A: anything with ``mult(x, y)``, ``block_diagonal()`` and ``bs``."""
         self.A = A
+        if self.M is not None:
+            self.M.update()
+            return
         D = A.block_diagonal()
         # rows without a diagonal block (none after assembly with bcs) keep identity
         eye = torch.eye(A.bs, dtype=D.dtype, device=D.device)
@@ -93,6 +107,10 @@ class KrylovSolver:
         self.Dinv = torch.linalg.inv(D)
 
     def _prec(self, r: torch.Tensor) -> torch.Tensor:
+        if self.M is not None:
+            if self._z is None or self._z.shape != r.shape or self._z.device != r.device:
+                self._z = torch.empty_like(r)
+            return self.M.apply(r, self._z)
         bs = self.A.bs
         return torch.bmm(self.Dinv, r.reshape(-1, bs, 1)).reshape(-1)
 

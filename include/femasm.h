@@ -387,6 +387,49 @@ int fa_jacobian_block_diag(const fa_mesh* mesh, const fa_form* form, const fa_ad
 int fa_apply_plan_bytes(const fa_mesh* mesh, const fa_adjacency* adj, int64_t* bytes, int64_t* nchunks, void* stream);
 int fa_apply_plan(const fa_mesh* mesh, const fa_adjacency* adj, void* buf, int64_t bytes, void* stream);
 
+/* ---- geometric multigrid: lattice transfers and the smoother step (femasm_mg.hip) ----
+ * Not a reference interface: the reference preconditions its Krylov solve with BoomerAMG
+ * (FEniCSx/mechanic2d/asym_elasto_damage_model.cc:720-813); these calls serve femasm.mg's geometric
+ * multigrid on the structured meshes instead.
+ *
+ * A transfer joins a coarse lattice of nc[d] + 1 points per axis to the fine lattice of 2 nc[d] + 1
+ * points (d < tdim; lattice index 0 fastest, the structured meshes' node numbering; dof = node * bs +
+ * comp, bs 1 to 3). P is linear interpolation on the right-diagonal triangle / Kuhn tetrahedron mesh
+ * (simplex = 1: a fine point I with odd mask o = I & 1 takes 1/2 of each of the coarse points
+ * (I - o) / 2 and (I + o) / 2, or copies its coarse point when o = 0) or multilinear interpolation
+ * (simplex = 0: the mean of the 2^|o| coarse points (I +- o) / 2). The same stencil is the P2 -> P1
+ * transfer on one mesh and the P1(h) -> P1(2h) transfer between a mesh and its refinement. */
+typedef struct {
+  int32_t tdim;    /* 2 or 3 */
+  int32_t simplex; /* 1: triangles / tetrahedra, 0: quadrilaterals / hexahedra */
+  int32_t bs;      /* dofs per lattice point */
+  int32_t _pad;
+  int64_t nc[3];   /* coarse cells per axis (entries d >= tdim are ignored) */
+} fa_transfer;
+
+/* xf (+)= M_f P M_c xc: M zeroes the dofs whose marker is nonzero (bc_c / bc_f, int8 per dof, either
+ * may be NULL). add = 0 overwrites xf (masked fine dofs receive 0), add != 0 adds into it (masked fine
+ * dofs are left alone). One thread per fine dof gathers its coarse values: no atomics. */
+int fa_prolong(const fa_transfer* t, const double* xc, const int8_t* bc_c /* or NULL */,
+               const int8_t* bc_f /* or NULL */, int32_t add, double* xf, void* stream);
+
+/* rc = M_c P^T M_f rf, the exact transpose of fa_prolong, as a gather per coarse dof: its own fine
+ * point plus, for simplices, the fine points at +o and -o of every nonzero 0/1 vector o (weight 1/2; at
+ * most 6 in 2-D, 14 in 3-D) or, for tensor cells, the 3^tdim - 1 neighbours (weight 2^-|o|); neighbours
+ * outside the lattice are skipped. Fixed summation order, no atomics: bit-reproducible. rc is
+ * overwritten. */
+int fa_restrict(const fa_transfer* t, const double* rf, const int8_t* bc_f /* or NULL */,
+                const int8_t* bc_c /* or NULL */, double* rc, void* stream);
+
+/* One fused step of the Chebyshev / block-Jacobi smoother over nnodes * bs dofs (bs 1 to 3):
+ *   d <- c_d d + c_r Dinv (b - Ax),   x <- x + d,
+ * Dinv [nnodes][bs][bs] row-major. c_d == 0 does not read d (the first step of a polynomial); Ax may be
+ * NULL for A x = 0 (a zero initial guess). One pass over the vectors. */
+int fa_cheb_step(int64_t nnodes, int32_t bs, const double* Dinv, const double* b, const double* Ax /* or NULL */,
+                 double c_d, double c_r, double* d, double* x, void* stream);
+
+/* None of the three allocates or synchronises; all index arithmetic is 64-bit. */
+
 /* Measurement helper (not part of the reference interface): a 16-B-per-lane grid-stride stream
  * over n doubles (n even, 16-B aligned buffers) for the measured HBM peak beside the 8 TB/s spec
  * (SURVEY.md section 8(d)). mode 0: dst = src (copy), 1: dst = 1.0 (write only), 2: read src
