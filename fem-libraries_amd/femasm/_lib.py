@@ -100,6 +100,18 @@ class fa_transfer(ctypes.Structure):
     ]
 
 
+class fa_edge_transfer(ctypes.Structure):
+    _fields_ = [
+        ("ncoarse", ctypes.c_int64),
+        ("nedges", ctypes.c_int64),
+        ("bs", ctypes.c_int32),
+        ("_pad", ctypes.c_int32),
+        ("edge_verts", ctypes.c_void_p),
+        ("vptr", ctypes.c_void_p),
+        ("vedges", ctypes.c_void_p),
+    ]
+
+
 # exported symbols with their signatures; tests check every one against include/femasm.h
 P = ctypes.c_void_p
 I32, I64, D = ctypes.c_int32, ctypes.c_int64, ctypes.c_double
@@ -140,6 +152,10 @@ SIGNATURES = {
     "fa_prolong": (ctypes.c_int, [P, P, P, P, I32, P, P]),
     "fa_restrict": (ctypes.c_int, [P, P, P, P, P, P]),
     "fa_cheb_step": (ctypes.c_int, [I64, I32, P, P, P, D, D, P, P, P]),
+    "fa_refine_cells": (ctypes.c_int, [I32, I64, I64, P, P, P, P, P, P, P]),
+    "fa_edge_midpoints": (ctypes.c_int, [I64, I32, P, P, P, P]),
+    "fa_prolong_edges": (ctypes.c_int, [P, P, P, P, I32, P, P]),
+    "fa_restrict_edges": (ctypes.c_int, [P, P, P, P, P, P]),
     "fa_hbm_probe": (ctypes.c_int, [I32, P, P, I64, P]),
 }
 

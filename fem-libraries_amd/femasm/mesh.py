@@ -76,6 +76,7 @@ class Mesh:
     cells: torch.Tensor  # [ncells, nverts_per_cell] int32 geometry / topology dofmap
     cell_tags: torch.Tensor | None = None  # [ncells] int32 physical tags (E per tag)
     structured: dict | None = field(default=None, repr=False)  # lattice info for fast dofmaps
+    parent: "Mesh | None" = field(default=None, repr=False)  # the mesh this one refines (refine)
 
     @property
     def gdim(self) -> int:
@@ -99,7 +100,8 @@ class Mesh:
 
     def to(self, device) -> "Mesh":
         return Mesh(self.cell_type, self.x.to(device), self.cells.to(device),
-                    None if self.cell_tags is None else self.cell_tags.to(device), self.structured)
+                    None if self.cell_tags is None else self.cell_tags.to(device), self.structured,
+                    None if self.parent is None else self.parent.to(device))
 
 
 def _lattice_vertices(n, lengths, device):
@@ -302,3 +304,105 @@ def locate_vertices(mesh: Mesh, marker) -> torch.Tensor:
     """Vertices whose coordinates satisfy marker(x) (x as [gdim, n], dolfinx convention)."""
     keep = marker(mesh.x.T)
     return torch.nonzero(keep, as_tuple=False).reshape(-1).to(torch.int32)
+
+
+# ---------------------------------------------------------------------------------- uniform refinement
+# Local vertex codes of a parent cell: its vertices 0 .. nv - 1, then the midpoints m01, m02, (m03,) m12,
+# (m13, m23); with the edge order of EDGES code nv + k is local edge n_local - 1 - k.
+_REFINE_TRI = ((0, 3, 4), (3, 1, 5), (4, 5, 2), (3, 5, 4))
+_REFINE_TET_CORNER = ((0, 4, 5, 6), (4, 1, 7, 8), (5, 7, 2, 9), (6, 8, 9, 3))
+# the four children around each diagonal of the inner octahedron (m01-m23, m02-m13, m03-m12); each child
+# is the diagonal plus one edge of the cycle through the other four midpoints, its vertices ordered so
+# that it keeps the parent's orientation sign
+_REFINE_TET_INNER = (
+    ((4, 5, 6, 9), (4, 6, 8, 9), (4, 7, 9, 8), (4, 5, 9, 7)),
+    ((4, 5, 6, 8), (4, 5, 8, 7), (5, 6, 8, 9), (5, 7, 9, 8)),
+    ((4, 5, 6, 7), (5, 6, 7, 9), (6, 7, 9, 8), (4, 6, 8, 7)),
+)
+_TET_DIAGONALS = (((0, 1), (2, 3)), ((0, 2), (1, 3)), ((0, 3), (1, 2)))
+_INT32_MAX = 2 ** 31 - 1
+
+
+def _refine_host(m: Mesh, ev: torch.Tensor, ce: torch.Tensor):
+    """Plain-torch refinement (the definition; any device): (x, cells, tags) of refine(m)."""
+    nv, nl = m.num_vertices, ce.shape[1]
+    c = m.cells.to(torch.int64)
+    x = torch.cat([m.x, 0.5 * (m.x[ev[:, 0]] + m.x[ev[:, 1]])], 0)
+    local = torch.cat([c, nv + ce.flip(1)], 1)  # [nc, nv_cell + nl] by local vertex code
+    if m.cell_type == CellType.triangle:
+        cells = local[:, torch.tensor(_REFINE_TRI, dtype=torch.int64, device=c.device)]
+    else:
+        X = m.x[c]  # [nc, 4, 3]
+        best, choice = None, torch.zeros(c.shape[0], dtype=torch.int64, device=c.device)
+        for g, ((a, b), (p, q)) in enumerate(_TET_DIAGONALS):
+            # every product and sum rounded on its own, in this order: fa_refine_cells computes the same bits
+            df = 0.5 * (X[:, a] + X[:, b]) - 0.5 * (X[:, p] + X[:, q])
+            sq = df * df
+            l2 = sq[:, 0] + sq[:, 1] + sq[:, 2]
+            if best is None:
+                best = l2
+            else:
+                less = l2 < best  # ties stay with the earlier diagonal
+                choice = torch.where(less, torch.full_like(choice, g), choice)
+                best = torch.where(less, l2, best)
+        table = torch.tensor([_REFINE_TET_CORNER + inner for inner in _REFINE_TET_INNER], dtype=torch.int64,
+                             device=c.device)  # [3, 8, 4]
+        cells = torch.gather(local[:, None, :].expand(-1, 8, -1), 2, table[choice])
+    nchild = cells.shape[1]
+    cells = cells.reshape(-1, c.shape[1]).to(torch.int32).contiguous()
+    tags = None if m.cell_tags is None else m.cell_tags.repeat_interleave(nchild).contiguous()
+    return x.contiguous(), cells, tags
+
+
+def refine(m: Mesh) -> Mesh:
+    """Regular ("red") refinement of a triangle or tetrahedron mesh (the reference scales its Gmsh mesh
+    this way: MAX_REFINE with refine, -r with UniformRefinement).
+
+    The parent's vertices keep their indices and coordinates; vertex ``nv + e`` is the midpoint of edge
+    ``e`` of ``entities(m, 1)``, which is the numbering of the degree-2 nodes of ``m``: the P1 space on
+    the result has the nodes of the P2 space on ``m``, in the same order. The children of cell ``c`` are
+    the cells ``c * 2^tdim + k`` (the parent of child ``j`` is ``j >> tdim``), with m_ij the midpoint of
+    local vertices i and j:
+
+      triangle     (v0,m01,m02) (m01,v1,m12) (m02,m12,v2) (m01,m12,m02)
+      tetrahedron  (v0,m01,m02,m03) (m01,v1,m12,m13) (m02,m12,v2,m23) (m03,m13,m23,v3), then the inner
+                   octahedron split along the shortest of its diagonals (lengths from the vertex
+                   coordinates, ties to the first):
+        m01-m23:   (m01,m02,m03,m23) (m01,m03,m13,m23) (m01,m12,m23,m13) (m01,m02,m23,m12)
+        m02-m13:   (m01,m02,m03,m13) (m01,m02,m13,m12) (m02,m03,m13,m23) (m02,m12,m23,m13)
+        m03-m12:   (m01,m02,m03,m12) (m02,m03,m12,m23) (m03,m12,m23,m13) (m01,m03,m13,m12)
+
+    Every child keeps its parent's orientation sign. ``cell_tags`` are inherited, ``structured`` is None,
+    ``parent`` is ``m``. A mesh on the GPU is refined by fa_refine_cells / fa_edge_midpoints, one on the
+    CPU by the same definition in torch; the two agree bit for bit."""
+    if m.cell_type not in (CellType.triangle, CellType.tetrahedron):
+        raise ValueError(f"refine serves triangles and tetrahedra, not {CellType(m.cell_type).name} cells")
+    ev, ce = entities(m, 1)
+    nv, ne, nc = m.num_vertices, int(ev.shape[0]), m.num_cells
+    nchild = 2 ** m.tdim
+    if nv + ne > _INT32_MAX:
+        raise ValueError(f"the refined mesh has {nv + ne} vertices: more than int32 holds")
+    if nc * nchild > _INT32_MAX:
+        raise ValueError(f"the refined mesh has {nc * nchild} cells: more than int32 holds")
+    if m.device.type != "cuda":
+        x, cells, tags = _refine_host(m, ev, ce)
+        return Mesh(m.cell_type, x, cells, tags, None, m)
+    from . import _lib
+
+    L = _lib.load()
+    dev = m.device
+    sh = _lib.stream_handle(dev)
+    gdim = m.gdim
+    ev32 = ev.to(torch.int32).contiguous()
+    ce32 = ce.to(torch.int32).contiguous()
+    mx, mc = m.x.contiguous(), m.cells.contiguous()
+    x = torch.empty((nv + ne, gdim), dtype=torch.float64, device=dev)
+    x[:nv] = mx
+    _lib.check(L.fa_edge_midpoints(ne, gdim, ev32.data_ptr(), mx.data_ptr(), x[nv:].data_ptr(), sh),
+               "fa_edge_midpoints")
+    cells = torch.empty((nc * nchild, mc.shape[1]), dtype=torch.int32, device=dev)
+    mt = None if m.cell_tags is None else m.cell_tags.to(torch.int32).contiguous()
+    tags = None if mt is None else torch.empty(nc * nchild, dtype=torch.int32, device=dev)
+    _lib.check(L.fa_refine_cells(int(m.cell_type), nc, nv, mc.data_ptr(), ce32.data_ptr(), mx.data_ptr(),
+                                 _lib.ptr(mt), cells.data_ptr(), _lib.ptr(tags), sh), "fa_refine_cells")
+    return Mesh(m.cell_type, x, cells, tags, None, m)

@@ -15,6 +15,13 @@ with odd mask ``o = I & 1`` takes, on simplices, half of each of the coarse poin
 ``(I + o) / 2`` (``o`` is always an edge direction of the mesh), and on tensor cells the mean of the
 ``2^|o|`` coarse points ``(I +- o) / 2``. ``fa_prolong`` / ``fa_restrict`` apply it (gathers, no atomics)
 and ``fa_cheb_step`` is the fused Chebyshev / block-Jacobi smoother update (femasm_mg.hip).
+
+Meshes without a lattice are served through ``mesh.refine``: it numbers the midpoint of edge ``e`` as
+vertex ``nv + e``, the numbering of the degree-2 nodes (``fem._generic_dofmap``), so the P1 nodes of
+``refine(m)`` are the P2 nodes of ``m`` and one edge stencil (an edge node takes half of each end vertex:
+``EdgeTransfer``, ``fa_prolong_edges`` / ``fa_restrict_edges`` in femasm_refine.hip) is again both the
+p- and the h-transfer. The hierarchy is the chain of ``mesh.parent`` (``plan_refined_hierarchy``);
+everything from ``update()`` down is shared with the lattice path.
 """
 from __future__ import annotations
 
@@ -71,6 +78,62 @@ class Transfer:
         for d in range(3):
             t.nc[d] = int(self.nc[d]) if d < self.tdim else 0
         return t
+
+
+class EdgeTransfer:
+    """``ncoarse`` coarse nodes <-> ``ncoarse + nedges`` fine nodes, fine node ``ncoarse + e`` sitting on
+    edge ``e`` of ``edge_verts`` [nedges, 2] (fa_edge_transfer); dof = node * bs + comp. With the edges of
+    ``mesh.entities(m, 1)`` this is the P2 -> P1 transfer on ``m`` and the P1 transfer between
+    ``mesh.refine(m)`` and ``m``. The edge-to-vertex CSR of the restriction (each coarse node's edges in
+    ascending order) is built here, once, on the device of ``edge_verts``."""
+
+    def __init__(self, edge_verts: torch.Tensor, ncoarse: int, bs: int):
+        ev = torch.as_tensor(edge_verts)
+        if ev.dim() != 2 or ev.shape[1] != 2 or ev.is_floating_point():
+            raise ValueError("edge_verts must be an integer tensor [nedges, 2]")
+        if not 1 <= int(bs) <= 3:
+            raise ValueError(f"block size {bs} (1 to 3)")
+        self.ncoarse, self.nedges, self.bs = int(ncoarse), int(ev.shape[0]), int(bs)
+        if self.ncoarse < 0 or self.ncoarse + self.nedges > 2 ** 31 - 1:
+            raise ValueError("the node count must be non-negative and fit int32")
+        if self.nedges and (int(ev.min()) < 0 or int(ev.max()) >= self.ncoarse):
+            raise ValueError(f"edge_verts must name coarse nodes 0 .. {self.ncoarse - 1}")
+        self.edge_verts = ev.to(torch.int32).contiguous()
+        flat = ev.reshape(-1).to(torch.int64)  # entry i belongs to edge i // 2
+        order = torch.sort(flat, stable=True).indices  # stable: a node's edges stay in ascending order
+        self.vedges = torch.div(order, 2, rounding_mode="floor").to(torch.int32).contiguous()
+        self.vptr = torch.zeros(self.ncoarse + 1, dtype=torch.int64, device=ev.device)
+        self.vptr[1:] = torch.cumsum(torch.bincount(flat, minlength=self.ncoarse), 0)
+        fa = _lib.fa_edge_transfer()
+        fa.ncoarse, fa.nedges, fa.bs = self.ncoarse, self.nedges, self.bs
+        fa.edge_verts, fa.vptr, fa.vedges = self.edge_verts.data_ptr(), self.vptr.data_ptr(), self.vedges.data_ptr()
+        self._desc = fa
+
+    @property
+    def num_coarse_dofs(self) -> int:
+        return self.ncoarse * self.bs
+
+    @property
+    def num_fine_dofs(self) -> int:
+        return (self.ncoarse + self.nedges) * self.bs
+
+    def _fa(self) -> _lib.fa_edge_transfer:
+        return self._desc
+
+
+def edge_transfer_matrix(t: EdgeTransfer):
+    """The prolongation P [fine dofs, coarse dofs] of an edge transfer as a scipy CSR matrix (host; tests
+    and debugging): the identity on the first ``ncoarse`` nodes, 1/2 and 1/2 on an edge node."""
+    import scipy.sparse as sp
+
+    ev = t.edge_verts.cpu().numpy().astype(np.int64)
+    nc, ne = t.ncoarse, t.nedges
+    rows = np.concatenate([np.arange(nc), nc + np.arange(ne), nc + np.arange(ne)])
+    cols = np.concatenate([np.arange(nc), ev[:, 0], ev[:, 1]])
+    vals = np.concatenate([np.ones(nc), np.full(2 * ne, 0.5)])
+    P = sp.coo_matrix((vals, (rows, cols)), shape=(nc + ne, nc)).tocsr()
+    P.sum_duplicates()
+    return sp.kron(P, sp.identity(t.bs), format="csr") if t.bs > 1 else P
 
 
 def _lattice_index(points, dims):
@@ -195,25 +258,61 @@ def plan_hierarchy(V: fem.FunctionSpace, coarse_dofs: int = 6000, max_levels: in
     return levels
 
 
+def plan_refined_hierarchy(V: fem.FunctionSpace, coarse_dofs: int = 6000, max_levels: int | None = None) -> list:
+    """Level table [(degree, mesh), ...] of a space on an unstructured simplex mesh: the space itself,
+    degree 1 on the same mesh if it has degree 2, then degree 1 on every ``mesh.parent`` (the chain
+    ``mesh.refine`` leaves behind), until a level has at most ``coarse_dofs`` dofs, ``max_levels`` levels
+    exist or the chain ends. ValueError for the spaces geometric multigrid cannot serve."""
+    m = V.mesh
+    if m.structured is not None:
+        raise ValueError("plan_refined_hierarchy serves meshes without a lattice; a structured mesh goes "
+                         "through plan_hierarchy")
+    if not fem.is_simplex(m.cell_type):
+        raise ValueError(f"GeometricMultigrid on an unstructured mesh needs triangles or tetrahedra, not "
+                         f"{CellType(m.cell_type).name} cells (mesh.refine serves simplices)")
+    if V.family in ("DG", "Discontinuous Lagrange") or V.degree not in (1, 2):
+        raise ValueError(f"GeometricMultigrid serves Lagrange degree 1 and 2, not {V.family} degree {V.degree}")
+    if max_levels is not None and max_levels < 1:
+        raise ValueError("max_levels must be at least 1")
+    ndofs = lambda p, k: (k.num_vertices + (int(fmesh.entities(k, 1)[0].shape[0]) if p == 2 else 0)) * V.bs
+    levels = [(V.degree, m)]
+    while (max_levels is None or len(levels) < max_levels) and ndofs(*levels[-1]) > coarse_dofs:
+        p, k = levels[-1]
+        if p == 2:
+            levels.append((1, k))
+        elif k.parent is not None:
+            levels.append((1, k.parent))
+        else:
+            break
+    if len(levels) == 1 and (max_levels is None or max_levels > 1) and ndofs(*levels[0]) > coarse_dofs:
+        raise ValueError(f"GeometricMultigrid needs a structured mesh (mesh.create_rectangle / create_box) or a "
+                         f"mesh made by mesh.refine: this degree-1 space has no parent mesh to coarsen to and its "
+                         f"{ndofs(1, m)} dofs exceed coarse_dofs={coarse_dofs}")
+    return levels
+
+
 class _Level:
     pass
 
 
-def _transfer_call(name, t: Transfer, *args):
+def _transfer_call(name, t, *args):
     fa = t._fa()
+    if isinstance(t, EdgeTransfer):
+        name += "_edges"
     _lib.check(getattr(_lib.load(), name)(ctypes.byref(fa), *args), name)
 
 
-def prolong(t: Transfer, xc: torch.Tensor, xf: torch.Tensor, bc_c=None, bc_f=None, add: bool = False) -> torch.Tensor:
-    """xf (+)= M_f P M_c xc (fa_prolong); markers int8 per dof or None."""
+def prolong(t, xc: torch.Tensor, xf: torch.Tensor, bc_c=None, bc_f=None, add: bool = False) -> torch.Tensor:
+    """xf (+)= M_f P M_c xc (fa_prolong for a Transfer, fa_prolong_edges for an EdgeTransfer); markers
+    int8 per dof or None."""
     _check_transfer_args(t, xc, xf, bc_c, bc_f)
     _transfer_call("fa_prolong", t, xc.data_ptr(), _lib.ptr(bc_c), _lib.ptr(bc_f), int(bool(add)), xf.data_ptr(),
                    _lib.stream_handle(xf.device))
     return xf
 
 
-def restrict(t: Transfer, rf: torch.Tensor, rc: torch.Tensor, bc_f=None, bc_c=None) -> torch.Tensor:
-    """rc = M_c P^T M_f rf (fa_restrict); bit-reproducible."""
+def restrict(t, rf: torch.Tensor, rc: torch.Tensor, bc_f=None, bc_c=None) -> torch.Tensor:
+    """rc = M_c P^T M_f rf (fa_restrict / fa_restrict_edges); bit-reproducible."""
     _check_transfer_args(t, rc, rf, bc_c, bc_f)
     _transfer_call("fa_restrict", t, rf.data_ptr(), _lib.ptr(bc_f), _lib.ptr(bc_c), rc.data_ptr(),
                    _lib.stream_handle(rc.device))
@@ -221,6 +320,8 @@ def restrict(t: Transfer, rf: torch.Tensor, rc: torch.Tensor, bc_f=None, bc_c=No
 
 
 def _check_transfer_args(t, c, f, bc_c, bc_f):
+    if isinstance(t, EdgeTransfer) and isinstance(f, torch.Tensor) and t.edge_verts.device != f.device:
+        raise ValueError(f"the transfer's edge table is on {t.edge_verts.device}, the fine vector on {f.device}")
     for name, v, n, dt in (("coarse vector", c, t.num_coarse_dofs, torch.float64),
                            ("fine vector", f, t.num_fine_dofs, torch.float64),
                            ("coarse marker", bc_c, t.num_coarse_dofs, torch.int8),
@@ -277,6 +378,12 @@ class GeometricMultigrid:
     ``coarse_dofs`` dofs is inverted densely at ``update()``, a larger one gets a fixed Chebyshev
     polynomial of degree 8.
 
+    On a mesh without a lattice (``mesh.structured is None``: triangles and tetrahedra) the levels follow
+    ``plan_refined_hierarchy``: degree 2 to degree 1 on the same mesh, then degree 1 on every
+    ``mesh.parent`` that ``mesh.refine`` left behind. The transfer is an ``EdgeTransfer``, injection takes
+    the first ``ncoarse`` nodes, the coarse marker is the leading slice of the fine one, the parent of cell
+    ``j`` is ``j >> tdim``; ``levels`` reports ``n = None``.
+
     ``update()`` must follow every change of the state (``KrylovSolver.set_operator`` calls it); the
     first ``apply`` runs it if nobody has. ``levels``: [(degree, n, num_dofs, kind)];
     ``operator_complexity``: stored matrix entries of all levels over those of the level-0 matrix."""
@@ -288,7 +395,8 @@ class GeometricMultigrid:
         if smoother_degree < 1:
             raise ValueError("smoother_degree must be at least 1")
         V = a.V
-        table = plan_hierarchy(V, coarse_dofs, max_levels)
+        refined = V.mesh.structured is None
+        table = (plan_refined_hierarchy if refined else plan_hierarchy)(V, coarse_dofs, max_levels)
         if V.bs != V.mesh.gdim:
             raise ValueError("the form's space must be a vector Lagrange space (bs = gdim)")
         self.a, self.V = a, V
@@ -303,7 +411,7 @@ class GeometricMultigrid:
         self._levels = []
         for li, (p, n) in enumerate(table):
             L = _Level()
-            L.degree, L.n = p, n
+            L.degree, L.n = p, (None if refined else n)
             if li == 0:
                 L.V, L.a = V, a
                 L.marker, _ = fem._combine_bcs(V, self.bcs, with_g=False)
@@ -312,17 +420,29 @@ class GeometricMultigrid:
                 L.kind = "matrix-free" if isinstance(L.A, fem.JacobianOperator) else "operator"
             else:
                 F = self._levels[-1]
-                if n == F.n:
-                    cm = F.V.mesh
-                elif m.tdim == 2:
-                    cm = fmesh.create_rectangle(st["lengths"], n, m.cell_type, st.get("diagonal", "right"), dev)
+                if refined:
+                    # n is the level's mesh: the same one below a degree-2 level, else the parent. Either
+                    # way the fine nodes are the coarse mesh's vertices, then one per edge of it
+                    cm = n
+                    F.transfer = EdgeTransfer(fmesh.entities(cm, 1)[0], cm.num_vertices, bs)
+                    if F.transfer.num_fine_dofs != F.V.num_dofs:
+                        raise ValueError("the mesh's parent does not have the numbering of mesh.refine")
+                    F.inject = slice(0, cm.num_vertices)
+                    F.parents = None if cm is F.V.mesh else \
+                        torch.arange(F.V.mesh.num_cells, device=dev, dtype=torch.int64) >> m.tdim
+                    L.marker = None if F.marker is None else F.marker[:F.transfer.num_coarse_dofs].contiguous()
                 else:
-                    cm = fmesh.create_box(st["lengths"], n, m.cell_type, dev)
+                    if n == F.n:
+                        cm = F.V.mesh
+                    elif m.tdim == 2:
+                        cm = fmesh.create_rectangle(st["lengths"], n, m.cell_type, st.get("diagonal", "right"), dev)
+                    else:
+                        cm = fmesh.create_box(st["lengths"], n, m.cell_type, dev)
+                    F.transfer = Transfer(m.tdim, simplex, bs, n)
+                    F.inject = injection_nodes(F.transfer, dev)
+                    F.parents = None if n == F.n else parent_cells(m.cell_type, n, dev)
+                    L.marker = coarsen_marker(F.marker, F.transfer)
                 L.V = fem.functionspace(cm, ("Lagrange", 1, (bs,)))
-                F.transfer = Transfer(m.tdim, simplex, bs, n)
-                F.inject = injection_nodes(F.transfer, dev)
-                F.parents = None if n == F.n else parent_cells(m.cell_type, n, dev)
-                L.marker = coarsen_marker(F.marker, F.transfer)
                 self._coarse_form(F, L)
                 L.A = fem.create_matrix(L.a)
                 L.kind = "assembled"

@@ -430,6 +430,55 @@ int fa_cheb_step(int64_t nnodes, int32_t bs, const double* Dinv, const double* b
 
 /* None of the three allocates or synchronises; all index arithmetic is 64-bit. */
 
+/* ---- uniform refinement of simplex meshes and the transfers over the refined hierarchy
+ * (femasm_refine.hip, fa_version() >= 104) ----
+ * The reference scales its Gmsh mesh by uniform refinement (MAX_REFINE with refine, -r with
+ * UniformRefinement); femasm.mesh.refine is regular ("red") refinement with a numbering chosen for the
+ * multigrid: the parent's vertices keep their indices, the midpoint of edge e (edges in the
+ * lexicographic order of their sorted vertex pair) is vertex nverts + e, the children of cell c are the
+ * cells c * 2^tdim + k. That is the numbering of the parent's degree-2 nodes, so the P1 space on the
+ * refined mesh has the nodes of the P2 space on the parent.
+ *
+ * fa_refine_cells: one thread per parent cell (FA_TRIANGLE: 4 children, FA_TETRAHEDRON: 8). cells
+ * [ncells][nv] vertices, cell_edges [ncells][nl] edge ids in basix's local edge order, x [nverts][3]
+ * vertex coordinates (tetrahedra only: the inner octahedron is split along the shortest of the diagonals
+ * m01-m23, m02-m13, m03-m12, ties to the first; may be NULL for triangles), tags [ncells] or NULL.
+ * Writes children [ncells * 2^tdim][nv] and, with tags, child_tags [ncells * 2^tdim]. Every child keeps
+ * its parent's orientation sign. With m_ij the midpoint of local vertices i and j:
+ *   triangle     (v0,m01,m02) (m01,v1,m12) (m02,m12,v2) (m01,m12,m02)
+ *   tetrahedron  (v0,m01,m02,m03) (m01,v1,m12,m13) (m02,m12,v2,m23) (m03,m13,m23,v3), then around
+ *     m01-m23:   (m01,m02,m03,m23) (m01,m03,m13,m23) (m01,m12,m23,m13) (m01,m02,m23,m12)
+ *     m02-m13:   (m01,m02,m03,m13) (m01,m02,m13,m12) (m02,m03,m13,m23) (m02,m12,m23,m13)
+ *     m03-m12:   (m01,m02,m03,m12) (m02,m03,m12,m23) (m03,m12,m23,m13) (m01,m03,m13,m12) */
+int fa_refine_cells(int32_t cell_type, int64_t ncells, int64_t nverts, const int32_t* cells,
+                    const int32_t* cell_edges, const double* x /* or NULL */, const int32_t* tags /* or NULL */,
+                    int32_t* children, int32_t* child_tags /* or NULL */, void* stream);
+
+/* xm[e][d] = 0.5 * (x[a][d] + x[b][d]) for edge e = (a, b) of edge_verts [nedges][2]; x [.][gdim], xm
+ * [nedges][gdim]. One thread per edge and component. */
+int fa_edge_midpoints(int64_t nedges, int32_t gdim, const int32_t* edge_verts, const double* x, double* xm,
+                      void* stream);
+
+/* Transfer between ncoarse coarse nodes and ncoarse + nedges fine nodes (dof = node * bs + comp): P is
+ * the identity on the first ncoarse fine nodes and 1/2, 1/2 on an edge node. */
+typedef struct {
+  int64_t ncoarse;            /* coarse nodes; fine nodes = ncoarse + nedges, fine node ncoarse + e is edge e */
+  int64_t nedges;
+  int32_t bs, _pad;           /* dofs per node, 1..3 */
+  const int32_t* edge_verts;  /* [nedges][2] coarse nodes of each edge */
+  const int64_t* vptr;        /* [ncoarse + 1] CSR: the edges of each coarse node ... */
+  const int32_t* vedges;      /* [2 nedges]    ... in ascending edge order */
+} fa_edge_transfer;
+
+/* xf (+)= M_f P M_c xc and rc = M_c P^T M_f rf with the marker and add rules of fa_prolong /
+ * fa_restrict. Both gather (one thread per output dof; the restriction sums a node's own fine dof, then
+ * its edges in vedges order, whatever the node's valence): no atomics, no allocation, no
+ * synchronisation, 64-bit index arithmetic, bit-reproducible. */
+int fa_prolong_edges(const fa_edge_transfer* t, const double* xc, const int8_t* bc_c /* or NULL */,
+                     const int8_t* bc_f /* or NULL */, int32_t add, double* xf, void* stream);
+int fa_restrict_edges(const fa_edge_transfer* t, const double* rf, const int8_t* bc_f /* or NULL */,
+                      const int8_t* bc_c /* or NULL */, double* rc, void* stream);
+
 /* Measurement helper (not part of the reference interface): a 16-B-per-lane grid-stride stream
  * over n doubles (n even, 16-B aligned buffers) for the measured HBM peak beside the 8 TB/s spec
  * (SURVEY.md section 8(d)). mode 0: dst = src (copy), 1: dst = 1.0 (write only), 2: read src

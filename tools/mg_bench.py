@@ -12,10 +12,19 @@
                     once with mg.GeometricMultigrid: iterations, seconds to solution, the multigrid
                     set-up (update()), ms per V-cycle and the share of it spent in the fine action.
 
+  --refine R        the same two modes on meshes without a lattice, made by mesh.refine. transfer: the
+                    tetrahedron box N^3 with its lattice record dropped, refined R times; the last
+                    refinement's fa_prolong_edges / fa_restrict_edges (bs 3) with the bytes they have to
+                    move (vectors, markers and index tables once each). solve: tests/golden/square.msh
+                    refined R times (or, with --box, the N^3 tetrahedron box without its lattice record),
+                    Lagrange --degree, E per physical tag, same bcs.
+
 Prints one JSON line.
 
   python tools/mg_bench.py --mode transfer --n 96 [--out profiles/multigrid/transfer_n96.json]
   python tools/mg_bench.py --mode solve --n 48 --rtol 1e-8 [--out profiles/multigrid/solve_n48.json]
+  python tools/mg_bench.py --mode transfer --n 48 --refine 1 [--out profiles/multigrid/edge_transfer_n48_r1.json]
+  python tools/mg_bench.py --mode solve --refine 3 --degree 1 --rtol 1e-10
 
 Fails when no GPU is found: a CPU run has no timing to give.
 """
@@ -84,17 +93,70 @@ def transfer_mode(args, dev) -> dict:
     return res
 
 
+def unstructured_box(n, dev) -> mesh.Mesh:
+    """The N^3 tetrahedron box without its lattice record: an unstructured mesh to the package."""
+    b = mesh.create_box((1.0, 1.0, 1.0), (n, n, n), mesh.CellType.tetrahedron, device=dev)
+    return mesh.Mesh(b.cell_type, b.x, b.cells, None, None)
+
+
+def edge_transfer_mode(args, dev) -> dict:
+    bs = 3
+    m = unstructured_box(args.n, dev)
+    for _ in range(args.refine - 1):
+        m = mesh.refine(m)
+    ev = mesh.entities(m, 1)[0]
+    t = mg.EdgeTransfer(ev, m.num_vertices, bs)
+    del ev
+    nf, nc, ne, nv = t.num_fine_dofs, t.num_coarse_dofs, t.nedges, t.ncoarse
+    g = torch.Generator().manual_seed(1)
+    rnd = lambda k: (torch.rand(k, generator=g, dtype=torch.float64) - 0.5).to(dev)
+    xc, xf, rc, rf = rnd(nc), rnd(nf), rnd(nc), rnd(nf)
+    mf = (torch.rand(nf, generator=g) < 0.05).to(torch.int8).to(dev)
+    mc = (torch.rand(nc, generator=g) < 0.05).to(torch.int8).to(dev)
+    even = nf - (nf & 1)
+    L, sh = _lib.load(), _lib.stream_handle(dev)
+    src, dst = rnd(even), torch.empty(even, dtype=torch.float64, device=dev)
+    pro_idx, res_idx = 8 * ne, 8 * (nv + 1) + 8 * ne  # edge_verts; vptr and vedges
+    calls = {
+        "hbm_copy": (lambda: _lib.check(L.fa_hbm_probe(0, dst.data_ptr(), src.data_ptr(), even, sh)), 16 * even),
+        "prolong": (lambda: mg.prolong(t, xc, xf), 8 * (nc + nf) + pro_idx),
+        "prolong_add": (lambda: mg.prolong(t, xc, xf, add=True), 8 * (nc + 2 * nf) + pro_idx),
+        "prolong_add_masked": (lambda: mg.prolong(t, xc, xf, bc_c=mc, bc_f=mf, add=True),
+                               8 * (nc + 2 * nf) + nc + nf + pro_idx),
+        "restrict": (lambda: mg.restrict(t, rf, rc), 8 * (nc + nf) + res_idx),
+        "restrict_masked": (lambda: mg.restrict(t, rf, rc, bc_f=mf, bc_c=mc), 8 * (nc + nf) + nc + nf + res_idx),
+    }
+    valence = t.vptr[1:] - t.vptr[:-1]
+    res = {"refine": args.refine, "fine_nodes": nv + ne, "coarse_nodes": nv, "edges": ne, "fine_dofs": nf,
+           "coarse_dofs": nc, "valence_max": int(valence.max()), "valence_mean": 2.0 * ne / nv}
+    for name, (fn, nbytes) in calls.items():
+        ms = timed(fn, args.steps, args.warmup)
+        res[name] = {"ms": ms, "bytes": int(nbytes), "GBps": nbytes / ms["median"] * 1e-6}
+    for name in calls:
+        if name != "hbm_copy":
+            res[name]["of_copy"] = res[name]["GBps"] / res["hbm_copy"]["GBps"]
+    return res
+
+
 def solve_mode(args, dev) -> dict:
     n = args.n
-    m = mesh.create_box((1.0, 1.0, 1.0), (n, n, n), mesh.CellType.tetrahedron, device=dev)
-    V = fem.functionspace(m, ("Lagrange", 2, (3,)))
-    cid = torch.arange(m.num_cells, device=dev, dtype=torch.int64)
+    if args.refine:
+        m = unstructured_box(n, dev) if args.box else \
+            mesh.read_gmsh(os.path.join(ROOT, "tests", "golden", "square.msh"), gdim=2, device=dev)
+        for _ in range(args.refine):
+            m = mesh.refine(m)
+        V = fem.functionspace(m, ("Lagrange", args.degree, (m.gdim,)))
+    else:
+        m = mesh.create_box((1.0, 1.0, 1.0), (n, n, n), mesh.CellType.tetrahedron, device=dev)
+        V = fem.functionspace(m, ("Lagrange", 2, (3,)))
+    cid = m.cell_tags.to(torch.int64) if m.cell_tags is not None else \
+        torch.arange(m.num_cells, device=dev, dtype=torch.int64)
     E = torch.tensor(e_range(), dtype=torch.float64, device=dev)[cid % 200]
     u = fem.Function(V)
     a = fem.LinearElasticity(V, E=E, nu=0.3, u=u)
     left = fem.locate_dofs_geometrical(V, lambda x: torch.isclose(x[0], torch.zeros_like(x[0])))
     right = fem.locate_dofs_geometrical(V, lambda x: torch.isclose(x[0], torch.ones_like(x[0])))
-    bcs = [fem.dirichletbc(0.0, left, V), fem.dirichletbc([0.01, 0.0, 0.0], right, V)]
+    bcs = [fem.dirichletbc(0.0, left, V), fem.dirichletbc([0.01] + [0.0] * (m.gdim - 1), right, V)]
     problem = nls.NonlinearProblem(a, u, bcs, matrix_free=True)
     b = torch.zeros(V.num_dofs, dtype=torch.float64, device=dev)
     problem.F(u.x, b)
@@ -105,7 +167,8 @@ def solve_mode(args, dev) -> dict:
         ks = nls.KrylovSolver(rtol=args.rtol, max_it=args.max_it)
         M = None
         if name == "mg":
-            M = mg.GeometricMultigrid(a, bcs, fine_operator=A, smoother_degree=args.smoother_degree)
+            M = mg.GeometricMultigrid(a, bcs, fine_operator=A, smoother_degree=args.smoother_degree,
+                                      coarse_dofs=args.coarse_dofs)
             ks.set_preconditioner(M)
         x = torch.zeros_like(b)
         torch.cuda.synchronize()
@@ -141,6 +204,10 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--mode", choices=("transfer", "solve"), default="transfer")
     ap.add_argument("--n", type=int, default=96)
+    ap.add_argument("--refine", type=int, default=0, help="refine an unstructured mesh this many times")
+    ap.add_argument("--box", action="store_true", help="solve --refine: the N^3 tetrahedron box, not square.msh")
+    ap.add_argument("--degree", type=int, default=2, help="solve --refine: Lagrange degree")
+    ap.add_argument("--coarse-dofs", type=int, default=6000)
     ap.add_argument("--rtol", type=float, default=1e-8)
     ap.add_argument("--max-it", type=int, default=20000)
     ap.add_argument("--smoother-degree", type=int, default=2)
@@ -153,7 +220,12 @@ def main():
     dev = torch.device("cuda", 0)
     res = {"tool": "mg_bench", "mode": args.mode, "n": args.n, "steps": args.steps, "warmup": args.warmup,
            "device": torch.cuda.get_device_name(0)}
-    res.update(transfer_mode(args, dev) if args.mode == "transfer" else solve_mode(args, dev))
+    if args.refine < 0:
+        sys.exit("mg_bench: --refine must not be negative")
+    if args.mode == "solve":
+        res.update(solve_mode(args, dev))
+    else:
+        res.update(edge_transfer_mode(args, dev) if args.refine else transfer_mode(args, dev))
     line = json.dumps(res)
     print(line)
     if args.out:
