@@ -1517,6 +1517,12 @@ struct GatherArgs {
   double amax;  // max |ahat| entry of the element (DevTables::amax)
   const uint64_t* pk;  // packed integer reference tensor (DevTables::pk) or NULL
   double pks, pkmax;   // its 1 / sqrt(D) and max |N|
+  // prepared records (fa_prepare_cells: pks sqrt|det J| Ji, sign word +1; k_gather_lin PREPD): the table
+  // items scale their record by |coef[c]| and take the sign of mu |J| from it; coef[c] = +-sqrt|mu_c|
+  // per cell (k_cell_coef). NULL with records that hold mu (k_cell_records_staged)
+  const double* coef;
+  const int64_t* dlist;  // prepared Dirichlet diagonal offsets (fa_prepare_diag) or NULL: k_bc_diag
+  int64_t ndlist;
   // contribution plan (fa_plan_contrib, k_gather_own) or NULL
   const int64_t* cw;       // [nchunks + 1] offsets of the chunks' word sections (u16 units)
   const int32_t* ccells;   // [nchunks][FA_OWN_CCAP] the chunk's distinct cells (-1 padded)
@@ -1524,9 +1530,11 @@ struct GatherArgs {
 };
 
 // The record of cell c for the gather (all kinds but the neo-Hookean tangents): see Rec.
-template <int GD, int NN, int NV, int NQ, int MAT>
+// GEOM (uniform-nu records only): the static record of the prepared state, gs sqrt|det J| Ji with sign
+// word +1 -- no material (the form's coefficient is not read); gs = the packed table's 1 / sqrt(D)
+template <int GD, int NN, int NV, int NQ, int MAT, bool GEOM = false>
 __device__ __forceinline__ void cell_record(const MeshView& M, const FormView& F, const double* __restrict__ tab, int64_t c,
-                                            double (&r)[Rec<GD, NV, NQ, MAT>::SIZE]) {
+                                            double (&r)[Rec<GD, NV, NQ, MAT>::SIZE], double gs = 1.0) {
   using R = Rec<GD, NV, NQ, MAT>;
 #pragma unroll
   for (int k = 0; k < R::SIZE; ++k) r[k] = 0.0;
@@ -1542,11 +1550,11 @@ __device__ __forceinline__ void cell_record(const MeshView& M, const FormView& F
       for (int j = 0; j < 3; ++j) r[7 + 3 * i + j] = H[i][j];
   } else if constexpr (MAT == MAT_LINU || MAT == MAT_AFFT) {
     static_assert(R::SIMP, "uniform-nu records: affine cells");
-    double lam, mu;
-    cell_lame(F, c, lam, mu);
+    double lam = 0.0, mu = 1.0;
+    if constexpr (!GEOM) cell_lame(F, c, lam, mu);
     double Ji[GD][GD];
     const double s2 = mu * fabs(MAT == MAT_AFFT ? affine_tensor_geometry<GD, NV>(M, c, Ji) : simplex_geometry<GD>(M, c, Ji));
-    const double sc = sqrt(fabs(s2));
+    const double sc = GEOM ? gs * sqrt(fabs(s2)) : sqrt(fabs(s2));
 #pragma unroll
     for (int i = 0; i < GD; ++i)
 #pragma unroll
@@ -1640,10 +1648,10 @@ __global__ __launch_bounds__(256) void k_cell_records(MeshView M, FormView F, co
 // damage law): a wave's 64 consecutive cells' records are one contiguous run; the lanes write them
 // into wave-private LDS and the wave stores the run with 16 B per lane (a lane storing its own
 // 80-B record touches one cache line per lane per store instruction). Config E: see DESIGN.md.
-template <int GD, int NN, int NV, int NQ, int MAT>
+template <int GD, int NN, int NV, int NQ, int MAT, bool GEOM = false>
 __global__ __launch_bounds__(256) void k_cell_records_staged(MeshView M, FormView F, const double* __restrict__ tab,
                                                              const int8_t* __restrict__ bc, double* __restrict__ rec,
-                                                             uint32_t* __restrict__ bcmask) {
+                                                             uint32_t* __restrict__ bcmask, double gs = 1.0) {
   using R = Rec<GD, NV, NQ, MAT>;
   static_assert(R::SIZE <= 16, "staged records: small records");
   __shared__ __attribute__((aligned(16))) double sbuf[4][64 * R::SIZE];
@@ -1654,7 +1662,7 @@ __global__ __launch_bounds__(256) void k_cell_records_staged(MeshView M, FormVie
     const bool valid = c < M.ncells;
     const int64_t cc = valid ? c : M.ncells - 1;
     double r[R::SIZE];
-    cell_record<GD, NN, NV, NQ, MAT>(M, F, tab, cc, r);
+    cell_record<GD, NN, NV, NQ, MAT, GEOM>(M, F, tab, cc, r, gs);
     uint32_t m = 0u;
     if (bcmask && bc && valid) m = cell_bcmask<GD, NN>(M, bc, c);  // (bc NULL: k_rec_bcbits adds the bits)
     // the mask also rides in the sign word (rec_sign; affine tensor cells too: k_gather_lin reads them)
@@ -1727,6 +1735,60 @@ __global__ __launch_bounds__(256) void k_rec_bcbits(const int64_t* __restrict__ 
         }
       }
     }
+  }
+}
+
+// ---- prepared cell state (fa_prepare_cells / fa_prepare_diag / fa_assemble_matrix_prepared) ----
+// A Newton or load-stepping loop assembles many times on one mesh with one set of constrained dofs; of
+// the uniform-nu record's inputs only the coefficient changes between those assemblies. The static
+// record (cell_record GEOM + k_rec_bcbits) is built once; every assembly runs only this pass, 8 B in and
+// 8 B out per cell: coef[c] = sign(mu_c) sqrt|mu_c|, the factor k_gather_lin's table items scale the
+// static record by (its sign is the sign of mu |J| that the record's sign word carried).
+__global__ __launch_bounds__(256) void k_cell_coef(FormView F, int64_t ncells, double* __restrict__ coef) {
+  for (int64_t c = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; c < ncells; c += (int64_t)gridDim.x * blockDim.x) {
+    double lam, mu;
+    cell_lame(F, c, lam, mu);
+    coef[c] = copysign(sqrt(fabs(mu)), mu);
+  }
+}
+
+// The Dirichlet diagonals of a row window as a list, once per (window, marker): for every constrained
+// dof of the window the offset of its diagonal value in the window's data (k_bc_diag's search, done
+// once). A thread per dof (a set-up kernel); the list's order is whatever the counter gives (every entry
+// receives the same value). A missing diagonal block raises error bit 2, as k_bc_diag does; entries
+// past the appended ones stay -1 (the caller presets the list) and are skipped.
+template <int GD>
+__global__ __launch_bounds__(256) void k_diag_list_build(BsrView A, const int8_t* __restrict__ bc, int64_t* __restrict__ off,
+                                                        int64_t cap, unsigned long long* __restrict__ cnt, int* err) {
+  const int64_t d0 = A.row_begin * GD, d1 = A.row_end * GD;
+  for (int64_t n = d0 + blockIdx.x * (int64_t)blockDim.x + threadIdx.x; n < d1; n += (int64_t)gridDim.x * blockDim.x) {
+    if (!bc[n]) continue;
+    const int64_t r = n / GD;
+    const int i = (int)(n % GD);
+    const int64_t s = find_slot(A.indptr, A.indices, r, (int32_t)r);
+    if (s < 0) {
+      atomicOr(err, 2);
+      continue;
+    }
+    const int64_t k = (int64_t)atomicAdd(cnt, 1ull);
+    if (k < cap) off[k] = (s - A.indptr[A.row_begin]) * GD * GD + i * GD + i;
+  }
+}
+// constrained dofs of a row window (the size of its diagonal list)
+__global__ __launch_bounds__(256) void k_diag_count(const int8_t* __restrict__ bc, int64_t d0, int64_t d1,
+                                                   unsigned long long* __restrict__ cnt) {
+  unsigned long long m = 0;
+  for (int64_t n = d0 + blockIdx.x * (int64_t)blockDim.x + threadIdx.x; n < d1; n += (int64_t)gridDim.x * blockDim.x)
+    m += bc[n] ? 1 : 0;
+  if (m) atomicAdd(cnt, m);
+}
+// dolfinx set_diagonal from the list, after the gather: one thread per offset
+__global__ __launch_bounds__(256) void k_set_diag_list(double* __restrict__ data, const int64_t* __restrict__ off, int64_t n,
+                                                      double diag) {
+  const int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (t < n) {
+    const int64_t o = off[t];
+    if (o >= 0) data[o] = diag;
   }
 }
 
@@ -2605,7 +2667,7 @@ __device__ __forceinline__ double pow2(int e) { return __hiloint2double((e + 102
 // fetched from beyond the L2 ~9 times (tools/r5/sim_l2.py: 8.7 modelled; 48.3 GB fetched per
 // launch against ~17 GB read once, profiles/r4/final_pmc_E.txt); Morton per XCD models 1.6.
 
-template <int GD, int NN, int NSPLIT, int NT = 256, bool FUSE = false, bool FIX = false>
+template <int GD, int NN, int NSPLIT, int NT = 256, bool FUSE = false, bool FIX = false, bool PREPD = false>
 __global__ __launch_bounds__(NT, NN == GD + 1 ? kLinWavesP1 : 4) void k_gather_lin(GatherArgs P, const uint32_t* __restrict__ zero32,
                                                         double* __restrict__ dump, int64_t per) {
   using R = Rec<GD, GD + 1, 1, MAT_LINU>;
@@ -2683,6 +2745,7 @@ __global__ __launch_bounds__(NT, NN == GD + 1 ? kLinWavesP1 : 4) void k_gather_l
     double r[RL];
     double x[FUSE ? NV1 : 1][GD];
     double E;
+    double cf;  // table items: the cell's coefficient +-sqrt|mu| (prepared records), or the table's 1 / sqrt(D)
     uint32_t sl[(NBG + 1) / 2];  // the item's slot words, two 16-bit words per register
     uint32_t mask;
   };
@@ -2717,6 +2780,8 @@ __global__ __launch_bounds__(NT, NN == GD + 1 ? kLinWavesP1 : 4) void k_gather_l
         it.r[2 * k] = v.x;
         it.r[2 * k + 1] = v.y;
       }
+      // prepared records: the cell's coefficient, one more static load per lane issued with the record's
+      if constexpr (PREPD) it.cf = P.coef[c];
     }
     const int64_t e = d.a0 + min(jit, max(d.na - 1, 0));
     load_slot_words<NN, NSPLIT>(P.slots, e, part, it.sl);
@@ -2726,8 +2791,14 @@ __global__ __launch_bounds__(NT, NN == GD + 1 ? kLinWavesP1 : 4) void k_gather_l
   // MAT_LINU branch on registers); table blocks: s Ji scaled by 1 / sqrt(D) of the packed table
   auto form_record = [&](Item& it) {
     if constexpr (!P1G) {
+      // s Ji / sqrt(D). Records that hold mu: times the table's scale. Prepared records (the scale folded
+      // in, sign word +1): times |coef| = sqrt|mu|, and the sign word takes the coefficient's sign
+      const double sa = PREPD ? fabs(it.cf) : P.pks;
 #pragma unroll
-      for (int kk = 0; kk < BS2; ++kk) it.r[kk] *= P.pks;
+      for (int kk = 0; kk < BS2; ++kk) it.r[kk] *= sa;
+      if constexpr (PREPD)
+        it.r[BS2] = __longlong_as_double(__double_as_longlong(it.r[BS2]) |
+                                         (__double_as_longlong(it.cf) & (long long)0x8000000000000000ull));
     }
     if constexpr (FUSE) {
       double J[GD][GD], Ji[GD][GD];
@@ -5225,10 +5296,23 @@ static int64_t gather_grid(K kernel, int64_t nchunks, int block = 256) {
 // one stage on a caller-owned work buffer (fa_gather_prepare / fa_gather_rows), or only report
 // that buffer's size.
 struct GatherStage {
-  enum { FULL, SIZE, PREP, ROWS } mode = FULL;
+  // prepared cell state (table items of k_gather_lin only; anything else: FA_E_UNSUPPORTED): SIZE_STATIC
+  // reports the static records' bytes, BUILD writes them (and their bc bits) into `work`, PREPARED
+  // gathers the plan's rows from `work` and the per-cell coefficients `coef`
+  enum { FULL, SIZE, PREP, ROWS, SIZE_STATIC, BUILD, PREPARED } mode = FULL;
   void* work = nullptr;
   int64_t* bytes = nullptr;
+  const double* coef = nullptr;
+  const int64_t* dlist = nullptr;  // PREPARED: the rows' Dirichlet diagonal list (or NULL: no bcs)
+  int64_t ndlist = 0;
+  bool fix = false;                // PREPARED: FA_DETERMINISTIC
+  int** err_out = nullptr;         // receives the stage's device error word (FA_CHECK_ERRORS)
+  bool prepared() const { return mode == SIZE_STATIC || mode == BUILD || mode == PREPARED; }
 };
+static int not_prepared() {
+  return fail(FA_E_UNSUPPORTED, "prepared cell state: only for the table gather of uniform-nu linear elasticity "
+                                "(P2 / P3 simplices, affine Q1 / Q2 quadrilaterals, Q1 hexahedra, positional plan)");
+}
 static inline int64_t align256(int64_t b) { return (b + 255) & ~int64_t(255); }
 
 // every node's coordinates and constrained-dof bits (bit j: dof node * GD + j), for the fused P1 records
@@ -5302,6 +5386,7 @@ static bool neo_m_plan_ok(const GatherArgs& P, int nsplit) {
 template <int GD, int NN, int NQ, int NSPLIT>
 static int launch_gather_neo(GatherArgs P, const int8_t* bc, hipStream_t s, const GatherStage& W) {
   using R = NeoM<GD, NQ>;
+  if (W.prepared()) return not_prepared();  // the neo-Hookean records depend on u
   const int64_t nc = P.M.ncells;
   const int64_t rec_bytes = align256((int64_t)sizeof(double) * R::count(nc));
   if (W.mode == GatherStage::SIZE) {
@@ -5441,6 +5526,35 @@ static int launch_gather(GatherArgs P, const int8_t* bc, hipStream_t s, const Ga
   }
   const int64_t nc = P.M.ncells;
   const int64_t rec_bytes = align256((int64_t)sizeof(double) * R::count(nc));
+  // the table items of k_gather_lin: the elements whose records split into a static part and a per-call
+  // coefficient (prepared cell state)
+  constexpr bool TABLE_LIN = (MAT == MAT_LINU || MAT == MAT_AFFT) && R::SIMP && NN % NSPLIT == 0 && NN * GD <= 32 &&
+                             NN < 64 && NN != GD + 1 && R::SIZE <= 16;
+  if (W.prepared()) {
+    if constexpr (!TABLE_LIN) return not_prepared();
+    else {
+      if (!P.pk) return not_prepared();
+      if (W.mode == GatherStage::SIZE_STATIC) {
+        *W.bytes = (int64_t)sizeof(double) * R::count(nc);
+        return FA_OK;
+      }
+      if (W.mode == GatherStage::BUILD) {
+        if (bc && !(P.adj_ptr && P.adj_idx)) return fail(FA_E_ARG, "fa_prepare_cells with bcs needs the adjacency");
+        if (nc > 0) {
+          k_cell_records_staged<GD, NN, NV, NQ, MAT, true><<<grid_for(nc), 256, 0, s>>>(
+              P.M, P.F, P.tab, nullptr, reinterpret_cast<double*>(W.work), nullptr, P.pks);
+          LAUNCH_CHECK();
+          if (bc && P.M.nnodes > 0) {
+            k_rec_bcbits<GD, NN, R::SIZE><<<grid_for((P.M.nnodes + 7) / 8), 256, 0, s>>>(
+                P.adj_ptr, P.adj_idx, bc, P.M.nnodes, reinterpret_cast<double*>(W.work), nullptr);
+            LAUNCH_CHECK();
+          }
+        }
+        return FA_OK;
+      }
+      P.coef = W.coef;
+    }
+  }
   if (W.mode == GatherStage::SIZE) {
     *W.bytes = rec_bytes + align256((int64_t)sizeof(uint32_t) * nc);
     return FA_OK;
@@ -5453,9 +5567,10 @@ static int launch_gather(GatherArgs P, const int8_t* bc, hipStream_t s, const Ga
     if (bc && (rc = scratch_alloc((void**)&mask, sizeof(uint32_t) * nc, s))) return rc;
   } else {
     rec = reinterpret_cast<double*>(W.work);
-    mask = bc ? reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(W.work) + rec_bytes) : nullptr;
+    mask = bc && W.mode != GatherStage::PREPARED ? reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(W.work) + rec_bytes)
+                                                 : nullptr;
   }
-  if (nc > 0 && W.mode != GatherStage::ROWS) {
+  if (nc > 0 && W.mode != GatherStage::ROWS && W.mode != GatherStage::PREPARED) {
     // uniform-nu records of <= 32 dofs: their bc bits from the constrained nodes (k_rec_bcbits), so the
     // records kernel reads no dofmap (config E: records 1.88 -> ~1.5 ms)
     constexpr bool NODE_BITS = (MAT == MAT_LINU || MAT == MAT_AFFT) && NN * GD <= 32 && R::SIZE <= 16;
@@ -5494,7 +5609,19 @@ static int launch_gather(GatherArgs P, const int8_t* bc, hipStream_t s, const Ga
       P.fixc = lin_fix_bound(GD, NN, rr, P.trc, P.pkmax);  // records scaled by 1 / sqrt(D): |N| bounds
       int64_t* ldesc = nullptr;
       if ((rc = lin_chunk_desc(P, &ldesc, s, seq))) return rc;
-      if (P.fix) {
+      bool prepd = false;  // static records + per-cell coefficients: the kernel's PREPD variants
+      if constexpr (TABLE_LIN) {
+        prepd = W.mode == GatherStage::PREPARED;
+        if (prepd && P.fix) {
+          const int64_t grid = gather_grid(k_gather_lin<GD, NN, NSPLIT, LNT, false, true, true>, P.nchunks, LNT);
+          k_gather_lin<GD, NN, NSPLIT, LNT, false, true, true><<<(unsigned)grid, LNT, 0, s>>>(P, zero32, dump, per8);
+        } else if (prepd) {
+          const int64_t grid = gather_grid(k_gather_lin<GD, NN, NSPLIT, LNT, false, false, true>, P.nchunks, LNT);
+          k_gather_lin<GD, NN, NSPLIT, LNT, false, false, true><<<(unsigned)grid, LNT, 0, s>>>(P, zero32, dump, per8);
+        }
+      }
+      if (prepd) {
+      } else if (P.fix) {
         const int64_t grid = gather_grid(k_gather_lin<GD, NN, NSPLIT, LNT, false, true>, P.nchunks, LNT);
         k_gather_lin<GD, NN, NSPLIT, LNT, false, true><<<(unsigned)grid, LNT, 0, s>>>(P, zero32, dump, per8);
       } else {
@@ -5503,7 +5630,12 @@ static int launch_gather(GatherArgs P, const int8_t* bc, hipStream_t s, const Ga
       }
       LAUNCH_CHECK();
       HIP_TRY(hipFreeAsync(ldesc, s));
-      if (bc) {  // Dirichlet diagonals (dolfinx set_diagonal) of the plan's rows
+      if (P.dlist) {  // Dirichlet diagonals from the prepared list (fa_prepare_diag)
+        if (P.ndlist > 0) {
+          k_set_diag_list<<<(unsigned)((P.ndlist + 255) / 256), 256, 0, s>>>(P.A.data, P.dlist, P.ndlist, P.diag);
+          LAUNCH_CHECK();
+        }
+      } else if (bc) {  // Dirichlet diagonals (dolfinx set_diagonal) of the plan's rows
         launch_bc_diag<GD>(P.A, (P.A.row_end - P.A.row_begin) * GD, bc, P.diag, P.err, s);
         LAUNCH_CHECK();
       }
@@ -5514,6 +5646,7 @@ static int launch_gather(GatherArgs P, const int8_t* bc, hipStream_t s, const Ga
       return FA_OK;
     }
   }
+  if (W.mode == GatherStage::PREPARED) return not_prepared();  // (a plan the table gather does not take)
   if (P.nchunks > 0 && W.mode != GatherStage::PREP) {
     if (P.fix)
       return fail(FA_E_UNSUPPORTED, "deterministic assembly runs the affine-simplex elasticity gather (uniform nu, "
@@ -5564,6 +5697,7 @@ static int launch_gather(GatherArgs P, const int8_t* bc, hipStream_t s, const Ga
 template <int NN, int NQ, int NSPLIT>
 static int launch_hex_gather(GatherArgs P, const DevTables& T, const int8_t* bc, hipStream_t s, const GatherStage& W) {
   const int64_t nc = P.M.ncells;
+  if (W.prepared()) return not_prepared();
   if (P.slot_order) {
     P.slots = nullptr;
     P.slot_order = 0;
@@ -5809,11 +5943,18 @@ static int gather_stage(const fa_mesh* mesh, const fa_form* form, const fa_adjac
     HIP_TRY(hipMemset(derr, 0, sizeof(int)));
   }
   P.err = derr;
+  if (W.err_out) *W.err_out = derr;
   if (adj && adj->ptr && adj->idx) {  // (the prepare stage: the records' bc bits from the nodes, k_rec_bcbits)
     P.adj_ptr = adj->ptr;
     P.adj_idx = adj->idx;
   }
-  if (W.mode == GatherStage::ROWS) {
+  if (W.mode == GatherStage::SIZE_STATIC || W.mode == GatherStage::BUILD) {
+    // no rows: the plan only says whether tensor cells are affine (their route to the table gather)
+    P.affine = plan && (plan->cell_flags & FA_PLAN_AFFINE) != 0;
+    P.pk = T.pk; P.pks = T.pk_scale;
+  }
+  if (W.mode == GatherStage::ROWS || W.mode == GatherStage::PREPARED) {
+    if (W.mode == GatherStage::PREPARED) P.affine = plan && (plan->cell_flags & FA_PLAN_AFFINE) != 0;
     if (!A || !A->indptr || !A->indices || !A->data) return fail(FA_E_ARG, "null matrix");
     if (A->bs != mesh->gdim || A->nrows != mesh->nnodes) return fail(FA_E_ARG, "matrix shape does not match mesh");
     int64_t wb = A->row_begin, we = A->row_end;
@@ -5830,6 +5971,11 @@ static int gather_stage(const fa_mesh* mesh, const fa_form* form, const fa_adjac
     P.amax = T.amax;
     P.pk = T.pk; P.pks = T.pk_scale; P.pkmax = T.pk_amax;
     set_contrib(P, plan);
+    if (W.mode == GatherStage::PREPARED) {
+      if (W.fix) P.fix = 1;
+      P.dlist = W.dlist;
+      P.ndlist = W.ndlist;
+    }
     if (P.fix && P.cw) return fail(FA_E_UNSUPPORTED, "deterministic assembly: not with a contribution plan");
   }
   bool handled = false;
@@ -5863,6 +6009,161 @@ extern "C" int fa_gather_rows(const fa_mesh* mesh, const fa_form* form, const fa
   W.mode = GatherStage::ROWS;
   W.work = const_cast<void*>(work);
   return gather_stage(mesh, form, adj, plan, bc, diag, A, W, (hipStream_t)stream);
+}
+
+// ------------------------------------------------------------------------------------ prepared cell state
+// fa_assemble_matrix(FA_GATHER) for the table gather with the per-cell work that does not change between
+// the assemblies of one mesh and one bcs set taken out of the call: see include/femasm.h.
+extern "C" int fa_prepared_bytes(const fa_mesh* mesh, const fa_form* form, const fa_plan* plan, int64_t* rec_bytes,
+                                 int64_t* coef_bytes) {
+  if (!rec_bytes || !coef_bytes) return fail(FA_E_ARG, "null size");
+  GatherStage W;
+  W.mode = GatherStage::SIZE_STATIC;
+  W.bytes = rec_bytes;
+  int rc = gather_stage(mesh, form, nullptr, plan, nullptr, 0.0, nullptr, W, nullptr);
+  if (rc) return rc;
+  *coef_bytes = (int64_t)sizeof(double) * mesh->ncells;
+  return FA_OK;
+}
+
+extern "C" int fa_prepare_cells(const fa_mesh* mesh, const fa_form* form, const fa_adjacency* adj, const fa_plan* plan,
+                                const int8_t* bc, fa_prepared* prepared, void* stream) {
+  if (!prepared || !prepared->rec) return fail(FA_E_ARG, "null prepared state");
+  GatherStage W;
+  W.mode = GatherStage::BUILD;
+  W.work = prepared->rec;
+  int rc = gather_stage(mesh, form, adj, plan, bc, 0.0, nullptr, W, (hipStream_t)stream);
+  if (rc) return rc;
+  prepared->has_bc = bc ? 1 : 0;
+  return FA_OK;
+}
+
+extern "C" int fa_prepare_coef(const fa_mesh* mesh, const fa_form* form, const fa_prepared* prepared, void* stream) {
+  int rc = check_mesh(mesh);
+  if (rc) return rc;
+  if (!prepared || !prepared->coef) return fail(FA_E_ARG, "null prepared state");
+  FormView F;
+  if ((rc = form_view(mesh, form, F))) return rc;
+  if (!lin_uniform_nu(F)) return not_prepared();
+  if (mesh->ncells > 0) {
+    k_cell_coef<<<grid_for(mesh->ncells), 256, 0, (hipStream_t)stream>>>(F, mesh->ncells, prepared->coef);
+    LAUNCH_CHECK();
+  }
+  return FA_OK;
+}
+
+static int diag_window(const fa_mesh* mesh, const fa_bsr* A, const int8_t* bc, int64_t* wb, int64_t* we) {
+  int rc = check_mesh(mesh);
+  if (rc) return rc;
+  if (!A || !A->indptr || !A->indices) return fail(FA_E_ARG, "null matrix");
+  if (A->bs != mesh->gdim || A->nrows != mesh->nnodes) return fail(FA_E_ARG, "matrix shape does not match mesh");
+  if (!bc) return fail(FA_E_ARG, "null bc marker");
+  *wb = A->row_begin;
+  *we = A->row_end;
+  if (*we <= *wb) { *wb = 0; *we = mesh->nnodes; }
+  if (*wb < 0 || *we > mesh->nnodes) return fail(FA_E_ARG, "row window out of range");
+  return FA_OK;
+}
+
+extern "C" int fa_prepare_diag_count(const fa_mesh* mesh, const fa_bsr* A, const int8_t* bc, int64_t* count, void* stream) {
+  int64_t wb, we;
+  int rc = diag_window(mesh, A, bc, &wb, &we);
+  if (rc) return rc;
+  if (!count) return fail(FA_E_ARG, "null count");
+  hipStream_t s = (hipStream_t)stream;
+  unsigned long long* dc = nullptr;
+  if ((rc = scratch_alloc((void**)&dc, sizeof(unsigned long long), s))) return rc;
+  HIP_TRY(hipMemsetAsync(dc, 0, sizeof(unsigned long long), s));
+  const int64_t n = (we - wb) * mesh->gdim;
+  if (n > 0) {
+    k_diag_count<<<grid_for(n), 256, 0, s>>>(bc, wb * mesh->gdim, we * mesh->gdim, dc);
+    LAUNCH_CHECK();
+  }
+  unsigned long long h = 0;
+  HIP_TRY(hipMemcpyAsync(&h, dc, sizeof(h), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  HIP_TRY(hipFreeAsync(dc, s));
+  *count = (int64_t)h;
+  return FA_OK;
+}
+
+extern "C" int fa_prepare_diag(const fa_mesh* mesh, const fa_bsr* A, const int8_t* bc, int64_t* offsets, int64_t count,
+                               void* stream) {
+  int64_t wb, we;
+  int rc = diag_window(mesh, A, bc, &wb, &we);
+  if (rc) return rc;
+  if (count < 0 || (count > 0 && !offsets)) return fail(FA_E_ARG, "null diagonal list");
+  if (count == 0) return FA_OK;
+  hipStream_t s = (hipStream_t)stream;
+  static int* derr = nullptr;  // device error word of the list builds (read by no one: FA_CHECK_ERRORS
+  if (!derr) {                 // assemblies validate the pattern themselves)
+    HIP_TRY(hipMalloc((void**)&derr, sizeof(int)));
+    HIP_TRY(hipMemset(derr, 0, sizeof(int)));
+  }
+  unsigned long long* dc = nullptr;
+  if ((rc = scratch_alloc((void**)&dc, sizeof(unsigned long long), s))) return rc;
+  HIP_TRY(hipMemsetAsync(dc, 0, sizeof(unsigned long long), s));
+  HIP_TRY(hipMemsetAsync(offsets, 0xFF, sizeof(int64_t) * (size_t)count, s));  // -1: no diagonal stored
+  BsrView Av{A->indptr, A->indices, A->data, wb, we};
+  const int64_t n = (we - wb) * mesh->gdim;
+  if (mesh->gdim == 2) k_diag_list_build<2><<<grid_for(n), 256, 0, s>>>(Av, bc, offsets, count, dc, derr);
+  else k_diag_list_build<3><<<grid_for(n), 256, 0, s>>>(Av, bc, offsets, count, dc, derr);
+  LAUNCH_CHECK();
+  int herr = 0;  // a constrained dof without a diagonal block: reported here, once, not per assembly
+  HIP_TRY(hipMemcpyAsync(&herr, derr, sizeof(int), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  HIP_TRY(hipFreeAsync(dc, s));
+  if (herr) {
+    HIP_TRY(hipMemset(derr, 0, sizeof(int)));
+    return fail(FA_E_PATTERN, "fa_prepare_diag: a constrained dof has no diagonal block in the pattern (error 0x%x)", herr);
+  }
+  return FA_OK;
+}
+
+extern "C" int fa_assemble_matrix_prepared(const fa_mesh* mesh, const fa_form* form, const fa_adjacency* adj,
+                                           const fa_plan* plan, const fa_prepared* prepared, double diag, fa_bsr* A,
+                                           int32_t flags, void* stream) {
+  if (!prepared || !prepared->rec || !prepared->coef) return fail(FA_E_ARG, "null prepared state");
+  if (flags & FA_SCATTER) return not_prepared();
+  if (prepared->has_bc && !prepared->diag_off && prepared->ndiag != 0)
+    return fail(FA_E_ARG, "prepared state with bcs needs its diagonal list (fa_prepare_diag)");
+  if (prepared->ndiag < 0 || prepared->ndiag >= (1ll << 39)) return fail(FA_E_ARG, "diagonal list size");
+  int rc;
+  if ((flags & FA_CHECK_ERRORS) && adj && adj->ptr && adj->idx && A &&
+      (rc = check_pattern(mesh, adj, A->indptr, A->indices, A->nblocks, false, stream)))
+    return rc;
+  hipStream_t s = (hipStream_t)stream;
+  int* derr = nullptr;
+  GatherStage W;
+  W.mode = GatherStage::PREPARED;
+  W.work = prepared->rec;
+  W.coef = prepared->coef;
+  W.dlist = prepared->has_bc ? prepared->diag_off : nullptr;
+  W.ndlist = prepared->has_bc ? prepared->ndiag : 0;
+  W.fix = (flags & FA_DETERMINISTIC) != 0;
+  W.err_out = &derr;
+  // the coefficient pass of this assembly, unless the caller ran it already (FA_KEEP_COEF: the further
+  // row parts of one assembly). After the argument checks of the rows stage would be tidier; a refused
+  // call then has only refreshed coef, which the next accepted call overwrites anyway.
+  if (!(flags & FA_KEEP_COEF) && (rc = fa_prepare_coef(mesh, form, prepared, stream))) return rc;
+  // (no marker: the records carry the bits and the list the diagonals)
+  if ((rc = gather_stage(mesh, form, adj, plan, nullptr, diag, A, W, s))) return rc;
+  if ((flags & FA_CHECK_ERRORS) && derr) {
+    int herr = 0;
+    HIP_TRY(hipMemcpyAsync(&herr, derr, sizeof(int), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (herr) {
+      HIP_TRY(hipMemset(derr, 0, sizeof(int)));
+      return fail(FA_E_PATTERN, "assembly kernel flagged error 0x%x (missing pattern entry / diagonal)", herr);
+    }
+  }
+  return FA_OK;
+}
+
+extern "C" int fa_gather_rows_prepared(const fa_mesh* mesh, const fa_form* form, const fa_adjacency* adj,
+                                       const fa_plan* plan, const fa_prepared* prepared, double diag, fa_bsr* A,
+                                       void* stream) {
+  return fa_assemble_matrix_prepared(mesh, form, adj, plan, prepared, diag, A, FA_GATHER | FA_KEEP_COEF, stream);
 }
 
 // ------------------------------------------------------------------------------------ vectors (next rows)

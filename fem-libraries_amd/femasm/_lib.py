@@ -18,6 +18,7 @@ FA_E_ARG, FA_E_UNSUPPORTED, FA_E_HIP, FA_E_PATTERN, FA_E_CAPACITY = -1, -2, -3, 
 FA_TRIANGLE, FA_QUADRILATERAL, FA_TETRAHEDRON, FA_HEXAHEDRON = 3, 4, -4, 8
 FA_LINEAR_ELASTICITY, FA_ASYM_DAMAGE, FA_NEO_HOOKEAN, FA_ASYM_DAMAGE_AD = 0, 1, 2, 3
 FA_GATHER, FA_SCATTER, FA_ZERO_FIRST, FA_DETERMINISTIC, FA_CHECK_ERRORS = 0x0, 0x1, 0x2, 0x4, 0x8
+FA_KEEP_COEF = 0x10
 FA_PLAN_AFFINE, FA_PLAN_DETERMINISTIC, FA_PLAN_ORDER_SEARCH, FA_PLAN_NEO = 0x1, 0x2, 0x4, 0x8
 FA_EVAL_GRAD, FA_EVAL_STRAIN, FA_EVAL_STRESS, FA_EVAL_ENERGY = 0x1, 0x2, 0x4, 0x8
 
@@ -90,6 +91,17 @@ class fa_plan(ctypes.Structure):
     ]
 
 
+class fa_prepared(ctypes.Structure):
+    _fields_ = [
+        ("rec", ctypes.c_void_p),
+        ("coef", ctypes.c_void_p),
+        ("diag_off", ctypes.c_void_p),
+        ("ndiag", ctypes.c_int64),
+        ("has_bc", ctypes.c_int32),
+        ("_pad", ctypes.c_int32),
+    ]
+
+
 class fa_transfer(ctypes.Structure):
     _fields_ = [
         ("tdim", ctypes.c_int32),
@@ -139,6 +151,13 @@ SIGNATURES = {
     "fa_gather_work_bytes": (ctypes.c_int, [P, P, P]),
     "fa_gather_prepare": (ctypes.c_int, [P, P, P, P, P]),
     "fa_gather_rows": (ctypes.c_int, [P, P, P, P, P, D, P, P, P]),
+    "fa_prepared_bytes": (ctypes.c_int, [P, P, P, P, P]),
+    "fa_prepare_cells": (ctypes.c_int, [P, P, P, P, P, P, P]),
+    "fa_prepare_diag_count": (ctypes.c_int, [P, P, P, P, P]),
+    "fa_prepare_diag": (ctypes.c_int, [P, P, P, P, I64, P]),
+    "fa_prepare_coef": (ctypes.c_int, [P, P, P, P]),
+    "fa_assemble_matrix_prepared": (ctypes.c_int, [P, P, P, P, P, D, P, I32, P]),
+    "fa_gather_rows_prepared": (ctypes.c_int, [P, P, P, P, P, D, P, P]),
     "fa_assemble_vector": (ctypes.c_int, [P, P, P, P, P]),
     "fa_eval_cells": (ctypes.c_int, [P, P, I32, P, P, I64, P, P, P, P, P]),
     "fa_apply_lifting": (ctypes.c_int, [P, P, P, P, P, P, P, D, P]),

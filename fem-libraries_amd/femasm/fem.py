@@ -104,6 +104,8 @@ def _geometry_basis(ct, X: np.ndarray) -> np.ndarray:
 class FunctionSpace:
     """Vector (bs = gdim) or scalar Lagrange space, or DG0 (per-cell) space."""
 
+    _prepared_builds = 0  # builds of the static part of a prepared cell state on this space (_prepared_state)
+
     def __init__(self, mesh: Mesh, family: str, degree: int, shape: tuple | None):
         self.mesh = mesh
         self.family = family
@@ -756,6 +758,82 @@ def _recheck_affine(V: FunctionSpace, key, plan):
     vers[key] = now
 
 
+class _Prepared:
+    """Prepared cell state of one (form kind, coordinates, dofmap, bc marker) on a space: the static
+    records (fa_prepare_cells), and per row window of a pattern its Dirichlet diagonal list
+    (fa_prepare_diag). The coefficient array is the space's (rewritten by every assembly)."""
+
+    def __init__(self, rec, coef, marker, has_bc):
+        self.rec, self.coef, self.marker, self.has_bc = rec, coef, marker, has_bc
+        self.windows = {}  # (indptr pointer, row_begin, row_end) -> (fa_prepared, offsets, indptr)
+
+    def window(self, V, fm, fb, indptr, sh):
+        key = (indptr.data_ptr(), int(fb.row_begin), int(fb.row_end))
+        hit = self.windows.get(key)
+        if hit is None:
+            L = _lib.load()
+            pp = _lib.fa_prepared(rec=self.rec.data_ptr(), coef=self.coef.data_ptr(), diag_off=None, ndiag=0,
+                                  has_bc=self.has_bc)
+            off = None
+            if self.has_bc:
+                n = ctypes.c_int64(0)
+                _lib.check(L.fa_prepare_diag_count(ctypes.byref(fm), ctypes.byref(fb), self.marker.data_ptr(),
+                                                   ctypes.byref(n), sh), "fa_prepare_diag_count")
+                if n.value > 0:
+                    off = torch.empty(n.value, dtype=torch.int64, device=V.mesh.device)
+                    _lib.check(L.fa_prepare_diag(ctypes.byref(fm), ctypes.byref(fb), self.marker.data_ptr(),
+                                                 off.data_ptr(), n.value, sh), "fa_prepare_diag")
+                    pp.diag_off, pp.ndiag = off.data_ptr(), n.value
+            if len(self.windows) >= 64:  # (row parts and split ranges of a few matrices)
+                self.windows.pop(next(iter(self.windows)))
+            hit = self.windows[key] = (pp, off, indptr)
+        return hit[0]
+
+
+def _prepared_state(V: FunctionSpace, a, marker, plan, fm, ff, sh):
+    """The prepared cell state for assembling `a` with this marker, built on a miss, or None when the
+    library does not take the form, element or plan (the caller then assembles as before). Held on V
+    like the plans; a hit needs the same form kind and quadrature, coordinates (tensor and version),
+    dofmap and marker (the tensor _combine_bcs returned, at the same version)."""
+    L = _lib.load()
+    if not hasattr(L, "fa_assemble_matrix_prepared"):  # (an older measurement build)
+        return None
+    if plan.contrib or not plan.eadj:  # the block-owner gather / a plan without positional items
+        return None
+    xver = _coords_version(V.mesh)
+    states = V.__dict__.setdefault("_prepared", {})
+    key = (a.kind, a.qdeg, a.E is not None, bool(plan.cell_flags & _lib.FA_PLAN_AFFINE), xver,
+           V.dofmap.data_ptr(), V.mesh.cells.data_ptr(),
+           None if marker is None else (id(marker), marker._version))
+    if key in states:
+        return states[key]
+    for k in [k for k in states if k[4] != xver]:  # records of coordinates that are gone
+        del states[k]
+    while len(states) >= 3:
+        states.pop(next(iter(states)))
+    nrec, ncoef = ctypes.c_int64(0), ctypes.c_int64(0)
+    rc = L.fa_prepared_bytes(ctypes.byref(fm), ctypes.byref(ff), ctypes.byref(plan), ctypes.byref(nrec),
+                             ctypes.byref(ncoef))
+    st = None
+    if rc != _lib.FA_E_UNSUPPORTED:
+        _lib.check(rc, "fa_prepared_bytes")
+        dev = V.mesh.device
+        coef = V.__dict__.get("_prepared_coef")
+        if coef is None or coef.numel() * 8 != max(ncoef.value, 8):
+            coef = V.__dict__["_prepared_coef"] = torch.empty(max(ncoef.value // 8, 1), dtype=torch.float64, device=dev)
+        rec = torch.empty(max(nrec.value // 8, 2), dtype=torch.float64, device=dev)
+        pp = _lib.fa_prepared(rec=rec.data_ptr(), coef=coef.data_ptr(), diag_off=None, ndiag=0, has_bc=0)
+        adj = V._fa_adjacency()
+        rc = L.fa_prepare_cells(ctypes.byref(fm), ctypes.byref(ff), ctypes.byref(adj), ctypes.byref(plan),
+                                _lib.ptr(marker), ctypes.byref(pp), sh)
+        if rc != _lib.FA_E_UNSUPPORTED:
+            _lib.check(rc, "fa_prepare_cells")
+            st = _Prepared(rec, coef, marker, int(pp.has_bc))
+            V._prepared_builds = V._prepared_builds + 1
+    states[key] = st
+    return st
+
+
 def assemble_matrix(a, bcs=None, diagonal: float = 1.0, A: MatrixCSR | None = None, method: str = "gather",
                     deterministic: bool = False, plan: dict | None = None, check: bool = False) -> MatrixCSR:
     """Assemble the bilinear form into a BSR matrix (dolfinx.fem.assemble_matrix + set_diagonal).
@@ -781,6 +859,7 @@ def assemble_matrix(a, bcs=None, diagonal: float = 1.0, A: MatrixCSR | None = No
     fm = V._fa_mesh()
     ff = _fa_form(a)
     sh = _lib.stream_handle(V.mesh.device)
+    prep, coef_done = None, False
     for part in range(len(A.parts)):
         fb = _fa_bsr(A, part)
         if method == "gather":
@@ -788,6 +867,20 @@ def assemble_matrix(a, bcs=None, diagonal: float = 1.0, A: MatrixCSR | None = No
             gp = gather_plan(V, A, part, a.kind, deterministic=deterministic, **(plan or {}))
             flags = _lib.FA_GATHER | (_lib.FA_DETERMINISTIC if deterministic else 0) | \
                 (_lib.FA_CHECK_ERRORS if check else 0)
+            # the prepared cell state (static records and diagonal lists kept on V; the coefficient pass
+            # once per assembly, not per part), where the library takes the form and the plan
+            if part == 0:
+                prep = _prepared_state(V, a, marker, gp, fm, ff, sh)
+            if prep is not None:
+                pp = prep.window(V, fm, fb, A.indptr, sh)
+                rc = L.fa_assemble_matrix_prepared(ctypes.byref(fm), ctypes.byref(ff), ctypes.byref(adj),
+                                                   ctypes.byref(gp), ctypes.byref(pp), float(diagonal), ctypes.byref(fb),
+                                                   flags | (_lib.FA_KEEP_COEF if coef_done else 0), sh)
+                if rc != _lib.FA_E_UNSUPPORTED:
+                    _lib.check(rc, "fa_assemble_matrix_prepared")
+                    coef_done = True
+                    continue
+                prep = None  # (a plan or a coefficient the prepared gather does not take: as before)
             rc = L.fa_assemble_matrix(ctypes.byref(fm), ctypes.byref(ff), ctypes.byref(adj), ctypes.byref(gp),
                                       _lib.ptr(marker), float(diagonal), ctypes.byref(fb), flags, sh)
         else:
@@ -953,7 +1046,9 @@ class SplitGather:
         nbytes = ctypes.c_int64(0)
         _lib.check(L.fa_gather_work_bytes(ctypes.byref(self.fm), ctypes.byref(self.ff), ctypes.byref(nbytes)),
                    "fa_gather_work_bytes")
-        self.work = torch.empty(max(int(nbytes.value), 16), dtype=torch.uint8, device=dev)
+        # the per-step records' buffer: allocated by the first prepare() that does not run on the
+        # prepared cell state (which keeps its static records on V instead)
+        self._work_bytes, self.work, self._prep = max(int(nbytes.value), 16), None, None
         pr0, pr1, data = A.parts[part]
         base = int(A.indptr[pr0])
         bs2 = A.bs * A.bs
@@ -1007,12 +1102,41 @@ class SplitGather:
                     _lib.check(self.L.fa_plan_check_affine(ctypes.byref(self.fm), ctypes.byref(plan), self.sh),
                                "fa_plan_check_affine")
             self._xver = now
+        # the prepared cell state of the space (shared with assemble_matrix): only the coefficient pass
+        # runs per step; the records and constrained-dof bits are rebuilt when the mesh or the marker change
+        live = [p for p in self.plans if p.nchunks > 0]
+        V = self.a.V
+        st = _prepared_state(V, self.a, self.marker, live[0], self.fm, self.ff, self.sh) if live else None
+        if st is not None:
+            pp = [st.window(V, self.fm, fb, self.A.indptr, self.sh) if p.nchunks > 0 else None
+                  for fb, p in zip(self.subs, self.plans)]
+            rc = self.L.fa_prepare_coef(ctypes.byref(self.fm), ctypes.byref(self.ff),
+                                        ctypes.byref(next(p for p in pp if p is not None)), self.sh)
+            if rc != _lib.FA_E_UNSUPPORTED:
+                _lib.check(rc, "fa_prepare_coef")
+                self._prep = pp
+                return
+        self._prep = None
+        self._prepare_records()
+
+    def _prepare_records(self):
+        if self.work is None:
+            self.work = torch.empty(self._work_bytes, dtype=torch.uint8, device=self.a.V.mesh.device)
         _lib.check(self.L.fa_gather_prepare(ctypes.byref(self.fm), ctypes.byref(self.ff), _lib.ptr(self.marker),
                                             self.work.data_ptr(), self.sh), "fa_gather_prepare")
 
     def rows(self, i: int):
         if self.plans[i].nchunks == 0:
             return
+        if self._prep is not None:
+            rc = self.L.fa_gather_rows_prepared(ctypes.byref(self.fm), ctypes.byref(self.ff), ctypes.byref(self.adj),
+                                                ctypes.byref(self.plans[i]), ctypes.byref(self._prep[i]), self.diagonal,
+                                                ctypes.byref(self.subs[i]), self.sh)
+            if rc != _lib.FA_E_UNSUPPORTED:
+                _lib.check(rc, "fa_gather_rows_prepared")
+                return
+            self._prep = None  # (a plan the prepared gather does not take: this step's records, as before)
+            self._prepare_records()
         _lib.check(self.L.fa_gather_rows(ctypes.byref(self.fm), ctypes.byref(self.ff), ctypes.byref(self.adj),
                                          ctypes.byref(self.plans[i]), _lib.ptr(self.marker), self.diagonal,
                                          self.work.data_ptr(), ctypes.byref(self.subs[i]), self.sh), "fa_gather_rows")

@@ -296,6 +296,58 @@ int fa_gather_prepare(const fa_mesh* mesh, const fa_form* form, const int8_t* bc
 int fa_gather_rows(const fa_mesh* mesh, const fa_form* form, const fa_adjacency* adj, const fa_plan* plan,
                    const int8_t* bc, double diag, const void* work, fa_bsr* A, void* stream);
 
+/* Prepared cell state (fa_version() >= 105): fa_assemble_matrix(FA_GATHER) with the per-cell work that
+ * stays the same across the assemblies of one mesh and one set of constrained dofs done once. A Newton
+ * or load-stepping loop (the reference's setJ callback, FEniCSx/mechanic2d/asym_elasto_damage_model.cc:
+ * 847-862, runs dolfinx assemble_matrix + set_diagonal at every iteration on one mesh with one bcs set)
+ * changes only the coefficient E between assemblies. For FA_LINEAR_ELASTICITY with E per cell and one
+ * Poisson ratio on the elements of the table gather (P2 / P3 triangles, P2 tetrahedra, affine Q1 / Q2
+ * quadrilaterals, affine Q1 hexahedra) with a positional plan; every other form, element or plan:
+ * FA_E_UNSUPPORTED from each call below, and the caller uses fa_assemble_matrix.
+ *   static  rec [ncells][gdim^2 + 1, rounded up to even] doubles: sqrt(|det J| / D) J^-1 (D the packed
+ *           reference table's denominator) and a word +1.0 holding the cell's constrained-dof bits in
+ *           its low mantissa bits. Valid while the coordinates, the geometry dofmap, the dofmap and the
+ *           bc marker are unchanged.
+ *   static  diag_off [ndiag]: per (row window of A, bc marker), the offset in the window's `data` of
+ *           every constrained dof's diagonal value (-1: skipped).
+ *   per call  coef [ncells]: sign(mu_c) sqrt|mu_c|, rewritten by every assembly from form->E (8 B read
+ *           and written per cell). Nothing keyed on the coefficient is kept.
+ * The caller owns all three buffers. fa_prepared_bytes (host only) returns the sizes of rec and coef;
+ * fa_prepare_diag_count the number of constrained dofs of A's row window (synchronises `stream`).
+ * fa_prepare_cells fills rec (bc may be NULL: no bits; with bc the adjacency is required; `plan`, which
+ * may be NULL for simplices, only says whether tensor cells are affine) and sets has_bc.
+ * fa_prepare_diag fills `offsets` (capacity `count`) for A's row window and synchronises `stream`:
+ * FA_E_PATTERN when a constrained dof has no diagonal block. fa_prepare_coef runs the coefficient pass
+ * alone. fa_assemble_matrix_prepared = coefficient pass, the row gather of `plan` from rec and coef,
+ * then `diag` stored at the listed offsets (nothing when has_bc is 0); the same values per row as
+ * fa_assemble_matrix up to rounding (sqrt|mu| * sqrt|det J| against sqrt|mu det J|: ~1 ulp per
+ * entry). It honours FA_DETERMINISTIC and FA_CHECK_ERRORS; FA_KEEP_COEF skips the coefficient pass
+ * (the further row parts of one assembly, after the first part's call or fa_prepare_coef).
+ * fa_gather_rows_prepared is fa_gather_rows on that state: the rows of `plan` (any sub-window of A,
+ * with its own diagonal list in `prepared`), no coefficient pass (fa_prepare_coef once per assembly
+ * takes the place of fa_gather_prepare). */
+#define FA_KEEP_COEF 0x10 /* fa_assemble_matrix_prepared: coef is already this assembly's */
+typedef struct {
+  double* rec;             /* static records */
+  double* coef;            /* per-call coefficients */
+  const int64_t* diag_off; /* diagonal offsets of A's row window, or NULL */
+  int64_t ndiag;
+  int32_t has_bc;          /* set by fa_prepare_cells: the records hold constrained-dof bits */
+  int32_t _pad;
+} fa_prepared;
+int fa_prepared_bytes(const fa_mesh* mesh, const fa_form* form, const fa_plan* plan, int64_t* rec_bytes,
+                      int64_t* coef_bytes);
+int fa_prepare_cells(const fa_mesh* mesh, const fa_form* form, const fa_adjacency* adj, const fa_plan* plan,
+                     const int8_t* bc, fa_prepared* prepared, void* stream);
+int fa_prepare_diag_count(const fa_mesh* mesh, const fa_bsr* A, const int8_t* bc, int64_t* count, void* stream);
+int fa_prepare_diag(const fa_mesh* mesh, const fa_bsr* A, const int8_t* bc, int64_t* offsets, int64_t count,
+                    void* stream);
+int fa_prepare_coef(const fa_mesh* mesh, const fa_form* form, const fa_prepared* prepared, void* stream);
+int fa_assemble_matrix_prepared(const fa_mesh* mesh, const fa_form* form, const fa_adjacency* adj, const fa_plan* plan,
+                                const fa_prepared* prepared, double diag, fa_bsr* A, int32_t flags, void* stream);
+int fa_gather_rows_prepared(const fa_mesh* mesh, const fa_form* form, const fa_adjacency* adj, const fa_plan* plan,
+                            const fa_prepared* prepared, double diag, fa_bsr* A, void* stream);
+
 /* Residual b += int sigma(u):eps(v) dx_q - int f.v dx_{2p} (b is ADDED into, like dolfinx
  * assemble_vector; the reference zeroes it first). sigma term on the form's quadrature degree
  * (the reference's `dxx`), load term on degree 2p (the reference's default `dx`). Node-parallel

@@ -28,14 +28,26 @@ for k, d in acc.items():
         print(f"  {c:24s} {mean:16.1f}{extra}  [{len(per)} dispatches]")
 
 
-LAUNCH_KERNELS = ("k_gather", "k_cell_records", "k_rec_bcbits", "k_neo_records", "k_hex_mfma", "k_bc_diag")  # one assembly launch
+LAUNCH_KERNELS = ("k_gather", "k_cell_records", "k_rec_bcbits", "k_neo_records", "k_hex_mfma", "k_bc_diag",
+                  "k_cell_coef", "k_set_diag_list")  # one assembly launch
+
+
+def launch_kernels(kernels=LAUNCH_KERNELS):
+    """The matching kernels that run in every assembly launch: a kernel with fewer dispatches than the
+    gather is set-up (the prepared cell state's records and bc bits are built by the first assembly
+    only) and is not part of a launch."""
+    n = {k: max(len({did for did, _ in vals}) for vals in d.values()) for k, d in acc.items()
+         if any(s in k for s in kernels)}
+    launches = min((c for k, c in n.items() if "k_gather" in k), default=0)
+    return {k for k, c in n.items() if c >= launches}
 
 
 def counter_total(name, kernels=LAUNCH_KERNELS):
     """Sum over the launch's kernels of the per-dispatch mean of one counter, or None if not collected."""
     tot, seen = 0.0, False
+    live = launch_kernels(kernels)
     for k, d in acc.items():
-        if not any(s in k for s in kernels) or name not in d:
+        if k not in live or name not in d:
             continue
         per = defaultdict(float)
         for did, v in d[name]:
@@ -48,8 +60,9 @@ def counter_total(name, kernels=LAUNCH_KERNELS):
 def traffic_record(root, kernels=LAUNCH_KERNELS):
     """HBM bytes per assembly launch: sum over the launch's kernels of FETCH_SIZE x 2 + WRITE_SIZE (KiB)."""
     tot = 0.0
+    live = launch_kernels(kernels)
     for k, d in acc.items():
-        if not any(s in k for s in kernels):
+        if k not in live:
             continue
         for c in ("FETCH_SIZE", "WRITE_SIZE"):
             if c not in d:

@@ -5,6 +5,9 @@
 set -o pipefail
 out=$1; kre=$2; shift 3
 mkdir -p "$out"
+# an assembly launch on the prepared cell state is the gather plus the coefficient pass
+# and the diagonal-list store: counted wherever the gather is
+case "$kre" in *k_gather*) kre="$kre|k_cell_coef|k_set_diag_list" ;; esac
 passes=(
   "FETCH_SIZE"
   "WRITE_SIZE TCC_HIT_sum TCC_MISS_sum"
