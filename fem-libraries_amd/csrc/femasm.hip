@@ -29,6 +29,7 @@
 #include <string>
 #include <tuple>
 #include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "../../include/femasm.h"
@@ -1422,11 +1423,6 @@ static constexpr int kGatherLdsNeo = FA_GATHER_LDS_NEO;
 constexpr int FA_NEO_NSPLIT = 2;  // neo-Hookean column items of 5 columns (E-neo at 2 waves / SIMD, round 2: NSPLIT 2
                                   // 342 ms, 5 at 3 waves 349, 10 at 4 waves 461; round 5: whole entries, 256
                                   // per chunk in a 72 KB accumulator, 64.1 vs 64.2 ms, plan 2.5 vs 1.5 s)
-// the neo-Hookean gather's item split per element (launch_gather's instantiations; its plans are
-// ordered for it and capped at 256 / split entries per chunk)
-static int neo_nsplit(int ct, int p) {
-  return ct == FA_TETRAHEDRON && p == 2 ? FA_NEO_NSPLIT : (ct == FA_TRIANGLE && p == 2 ? 2 : 1);
-}
 constexpr int FA_GATHER_ENTRY_CAP = 512;  // adjacency entries per chunk of the default plan (512 = the LDS arrays' cap)
 // blocks of the accumulator of a gather kernel (the plan's chunks must fit it)
 __host__ __device__ constexpr int gather_maxb(bool neo, int bs2) {
@@ -3797,6 +3793,7 @@ __global__ void k_row_ptr_from_sorted(const int32_t* __restrict__ keys, int64_t 
   }
 }
 
+// ------------------------------------------------------------------------------------ host utilities
 // AMD dispatches are limited to < 2^32 work-items in total (a larger grid fails silently),
 // so grids are capped and every kernel is written grid-stride.
 static int grid_for(int64_t n, int block = 256) {
@@ -3804,6 +3801,78 @@ static int grid_for(int64_t n, int block = 256) {
   if (g < 1) g = 1;
   if (g > kMaxBlocks) g = kMaxBlocks;
   return (int)g;
+}
+
+static inline int64_t align256(int64_t b) { return (b + 255) & ~int64_t(255); }
+
+// scratch for per-cell records: stream-ordered, from a pool that keeps its memory
+static int scratch_alloc(void** p, size_t bytes, hipStream_t s) {
+  static bool pool_set = false;
+  if (!pool_set) {
+    int dev = 0;
+    hipMemPool_t pool;
+    if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetDefaultMemPool(&pool, dev) == hipSuccess) {
+      uint64_t thr = UINT64_MAX;
+      (void)hipMemPoolSetAttribute(pool, hipMemPoolAttrReleaseThreshold, &thr);
+    }
+    pool_set = true;
+  }
+  HIP_TRY(hipMallocAsync(p, bytes > 0 ? bytes : 16, s));
+  return FA_OK;
+}
+
+// A scratch_alloc allocation that goes back to the pool on every path: the destructor frees it on its
+// stream (the pool never releases memory, so a refusal that forgot its buffer kept it for good).
+// Success paths call free(), which reports a failing hipFreeAsync.
+class Scratch {
+ public:
+  Scratch() = default;
+  Scratch(Scratch&& o) noexcept : p_(o.p_), s_(o.s_) { o.p_ = nullptr; }  // move-only: no copies are declared
+  ~Scratch() { if (p_) (void)hipFreeAsync(p_, s_); }  // (not free(): it must not replace the path's error text)
+  int alloc(size_t bytes, hipStream_t s) {  // (of an empty holder)
+    s_ = s;
+    return scratch_alloc(&p_, bytes, s);
+  }
+  int free() {
+    void* p = std::exchange(p_, nullptr);
+    if (p) HIP_TRY(hipFreeAsync(p, s_));
+    return FA_OK;
+  }
+  template <class T>
+  T* as() const { return reinterpret_cast<T*>(p_); }
+
+ private:
+  void* p_ = nullptr;
+  hipStream_t s_ = nullptr;
+};
+
+// per-chunk block / adjacency offsets: one dependent load level less in the gather's pipeline
+__global__ void k_chunk_desc(const int64_t* __restrict__ row_start, int64_t nchunks, const int64_t* __restrict__ indptr,
+                             const int64_t* __restrict__ adj_ptr, int64_t* __restrict__ cb, int64_t* __restrict__ ca) {
+  for (int64_t c = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; c <= nchunks; c += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t r = row_start[c];
+    cb[c] = indptr[r];
+    ca[c] = adj_ptr[r];
+  }
+}
+
+// k_gather_lin's chunk arrays: per chunk c, chunk_b[c] = its first block relative to the window,
+// chunk_a[c] = its first adjacency entry (clamped below the entry count, so a lane's entry load is
+// always in range) and chunk_a[nchunks + 1 + c] = block count | entry count << 32: three scalar
+// loads per chunk, no dependent level, and fewer pointers live in the kernel's loop
+// Position i of the arrays describes chunk seq[i] (the plan's visiting order) or chunk i (seq NULL).
+__global__ void k_lin_chunk_desc(const int64_t* __restrict__ row_start, int64_t nchunks, const int64_t* __restrict__ indptr,
+                                 int64_t row_begin, const int64_t* __restrict__ adj_ptr, int64_t nent,
+                                 const int32_t* __restrict__ seq, int64_t* __restrict__ cb, int64_t* __restrict__ ca) {
+  const int64_t base = indptr[row_begin];
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < nchunks; i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t c = seq ? (int64_t)seq[i] : i;
+    const int64_t r0 = row_start[c], r1 = row_start[c + 1];
+    const int64_t b0 = indptr[r0], a0 = adj_ptr[r0];
+    cb[i] = b0 - base;
+    ca[i] = min(a0, max(nent - 1, (int64_t)0));
+    ca[nchunks + 1 + i] = (int64_t)((uint64_t)(uint32_t)(indptr[r1] - b0) | ((uint64_t)(uint32_t)(adj_ptr[r1] - a0) << 32));
+  }
 }
 
 static int check_mesh(const fa_mesh* m) {
@@ -4036,7 +4105,6 @@ extern "C" int fa_sparsity_fill(const fa_mesh* mesh, const fa_adjacency* adj, co
 // slot map: thread per row node; for each adjacency entry of the row and each column node of the
 // cell, the position of that column in the row (binary search once, at plan time)
 // ------------------------------------------------------------------------------ pattern check
-static int scratch_alloc(void** p, size_t bytes, hipStream_t s);
 // fa_check_pattern: the sparsity pattern and the node -> cell adjacency are built with rocPRIM sorts
 // and scans (whose gfx950 code the library does not control, tools/store_hazard.py); this validates
 // both on the device. One thread per row: indptr monotone, columns in range and strictly increasing;
@@ -4496,6 +4564,18 @@ constexpr int FA_Q2QUAD_NT = 128;
 __host__ __device__ constexpr int lin_threads(int gd, int nn) {
   return gd == 3 && nn == 4 ? FA_P1TET_NT : gd == 3 && nn == 10 ? FA_P2TET_NT : gd == 2 && nn == 9 ? FA_Q2QUAD_NT : 256;
 }
+// The simplex elements of the row gather, once: what fa_plan_order orders a plan for (nsplit: the
+// linear kernels, lin_simplex_nsplit; neo: the neo-Hookean gather, neo_nsplit) is what dispatch_gather
+// instantiates (for_simplex_shape). The two splits differ for P2 tetrahedra only.
+struct SimplexShape {
+  int ct, p, nq, gd, nn, nv, nsplit, neo;
+};
+constexpr SimplexShape kSimplexShapes[4] = {
+    {FA_TRIANGLE, 1, 1, 2, 3, 3, 1, 1},
+    {FA_TRIANGLE, 2, 3, 2, 6, 3, 2, 2},
+    {FA_TETRAHEDRON, 1, 1, 3, 4, 4, FA_P1TET_NSPLIT, FA_P1TET_NSPLIT},
+    {FA_TETRAHEDRON, 2, 4, 3, 10, 4, FA_P2TET_NSPLIT, FA_NEO_NSPLIT},
+};
 static int lin_simplex_nsplit(int ct, int p, int nq, bool affine = false) {
   // affine hexahedra (MAT_AFFT): Q1 / Q2 / Q3 with their default rules
   if (affine && ct == FA_HEXAHEDRON && p == 1 && nq == 8) return 2;
@@ -4504,11 +4584,16 @@ static int lin_simplex_nsplit(int ct, int p, int nq, bool affine = false) {
   if (affine && ct == FA_QUADRILATERAL && p == 1 && nq == 4) return 1;
   if (affine && ct == FA_QUADRILATERAL && p == 2 && nq == 9) return FA_Q2QUAD_NSPLIT;
   if (affine && ct == FA_QUADRILATERAL && p == 3 && nq == 16) return 4;
-  if (ct == FA_TRIANGLE && p == 1 && nq == 1) return 1;
-  if (ct == FA_TRIANGLE && p == 2 && nq == 3) return 2;
-  if (ct == FA_TETRAHEDRON && p == 1 && nq == 1) return FA_P1TET_NSPLIT;
-  if (ct == FA_TETRAHEDRON && p == 2 && nq == 4) return FA_P2TET_NSPLIT;
+  for (const SimplexShape& e : kSimplexShapes)
+    if (ct == e.ct && p == e.p && nq == e.nq) return e.nsplit;
   return 0;
+}
+// the neo-Hookean gather's item split per element (its plans are ordered for it and capped at
+// 256 / split entries per chunk); 1 for an element it does not take
+static int neo_nsplit(int ct, int p) {
+  for (const SimplexShape& e : kSimplexShapes)
+    if (ct == e.ct && p == e.p) return e.neo;
+  return 1;
 }
 
 extern "C" int fa_plan_order(const fa_mesh* mesh, const fa_adjacency* adj, const fa_bsr* A, int32_t* eadj,
@@ -4793,9 +4878,6 @@ extern "C" int fa_plan_gather_form(const fa_mesh* mesh, int32_t kind, const fa_a
 }
 
 // ------------------------------------------------------------------------------- contribution plan
-static inline int64_t align256(int64_t b);
-__global__ void k_chunk_desc(const int64_t* __restrict__ row_start, int64_t nchunks, const int64_t* __restrict__ indptr,
-                             const int64_t* __restrict__ adj_ptr, int64_t* __restrict__ cb, int64_t* __restrict__ ca);
 // Chunking for k_gather_own: its output staging holds own_maxb blocks and its record staging
 // FA_OWN_CCAP cells (<= adjacency entries of the chunk).
 extern "C" int fa_plan_gather_contrib(const fa_mesh* mesh, const fa_adjacency* adj, const fa_bsr* A,
@@ -5013,8 +5095,6 @@ static void set_contrib(GatherArgs& P, const fa_plan* plan) {
 }
 
 // ------------------------------------------------------------------------------- chunk locality order
-static int scratch_alloc(void** p, size_t bytes, hipStream_t s);
-static inline int64_t align256(int64_t b);
 // Doubles <-> order-preserving unsigned keys (for atomic min / max of coordinates).
 __device__ inline unsigned long long ordered_key(double v) {
   const unsigned long long b = (unsigned long long)__double_as_longlong(v);
@@ -5137,9 +5217,6 @@ extern "C" int fa_plan_locality(const fa_mesh* mesh, const fa_adjacency* adj, in
 
 // The plan's chunk arrays once (fa_plan_chunk_desc): k_lin_chunk_desc as a launch would run it, into a
 // caller-owned buffer kept with the plan.
-__global__ void k_lin_chunk_desc(const int64_t* __restrict__ row_start, int64_t nchunks, const int64_t* __restrict__ indptr,
-                                 int64_t row_begin, const int64_t* __restrict__ adj_ptr, int64_t nent,
-                                 const int32_t* __restrict__ seq, int64_t* __restrict__ cb, int64_t* __restrict__ ca);
 extern "C" int fa_plan_chunk_desc(const fa_mesh* mesh, const fa_adjacency* adj, const fa_bsr* A, fa_plan* plan,
                                   int64_t* buf, void* stream) {
   int rc = check_mesh(mesh);
@@ -5189,85 +5266,42 @@ static int form_view(const fa_mesh* mesh, const fa_form* form, FormView& F) {
   return FA_OK;
 }
 
-// scratch for per-cell records: stream-ordered, from a pool that keeps its memory
-static int scratch_alloc(void** p, size_t bytes, hipStream_t s) {
-  static bool pool_set = false;
-  if (!pool_set) {
-    int dev = 0;
-    hipMemPool_t pool;
-    if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetDefaultMemPool(&pool, dev) == hipSuccess) {
-      uint64_t thr = UINT64_MAX;
-      (void)hipMemPoolSetAttribute(pool, hipMemPoolAttrReleaseThreshold, &thr);
-    }
-    pool_set = true;
-  }
-  HIP_TRY(hipMallocAsync(p, bytes > 0 ? bytes : 16, s));
-  return FA_OK;
-}
-
-// per-chunk block / adjacency offsets: one dependent load level less in the gather's pipeline
-__global__ void k_chunk_desc(const int64_t* __restrict__ row_start, int64_t nchunks, const int64_t* __restrict__ indptr,
-                             const int64_t* __restrict__ adj_ptr, int64_t* __restrict__ cb, int64_t* __restrict__ ca) {
-  for (int64_t c = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; c <= nchunks; c += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t r = row_start[c];
-    cb[c] = indptr[r];
-    ca[c] = adj_ptr[r];
-  }
-}
-
-static int chunk_desc(GatherArgs& P, int64_t** buf, hipStream_t s) {
+// k_gather's chunk arrays and XCD counters (zeroed), in scratch that `buf` owns
+static int chunk_desc(GatherArgs& P, Scratch& buf, hipStream_t s) {
   int rc;
   if (P.nchunks >= (1ll << 31)) return fail(FA_E_CAPACITY, "gather plan has %lld chunks (>= 2^31)", (long long)P.nchunks);
-  if ((rc = scratch_alloc((void**)buf, sizeof(int64_t) * (2 * (P.nchunks + 1) + 8), s))) return rc;
-  P.chunk_b = *buf;
-  P.chunk_a = *buf + (P.nchunks + 1);
-  P.ctr = reinterpret_cast<unsigned long long*>(*buf + 2 * (P.nchunks + 1));
+  if ((rc = buf.alloc(sizeof(int64_t) * (2 * (P.nchunks + 1) + 8), s))) return rc;
+  int64_t* d = buf.as<int64_t>();
+  P.chunk_b = d;
+  P.chunk_a = d + (P.nchunks + 1);
+  P.ctr = reinterpret_cast<unsigned long long*>(d + 2 * (P.nchunks + 1));
   HIP_TRY(hipMemsetAsync(P.ctr, 0, 8 * sizeof(unsigned long long), s));
-  k_chunk_desc<<<grid_for(P.nchunks + 1), 256, 0, s>>>(P.row_start, P.nchunks, P.A.indptr, P.adj_ptr, *buf,
-                                                      *buf + (P.nchunks + 1));
+  k_chunk_desc<<<grid_for(P.nchunks + 1), 256, 0, s>>>(P.row_start, P.nchunks, P.A.indptr, P.adj_ptr, d, d + (P.nchunks + 1));
   LAUNCH_CHECK();
   return FA_OK;
 }
 
-// k_gather_lin's chunk arrays: per chunk c, chunk_b[c] = its first block relative to the window,
-// chunk_a[c] = its first adjacency entry (clamped below the entry count, so a lane's entry load is
-// always in range) and chunk_a[nchunks + 1 + c] = block count | entry count << 32: three scalar
-// loads per chunk, no dependent level, and fewer pointers live in the kernel's loop
-// Position i of the arrays describes chunk seq[i] (the plan's visiting order) or chunk i (seq NULL).
-__global__ void k_lin_chunk_desc(const int64_t* __restrict__ row_start, int64_t nchunks, const int64_t* __restrict__ indptr,
-                                 int64_t row_begin, const int64_t* __restrict__ adj_ptr, int64_t nent,
-                                 const int32_t* __restrict__ seq, int64_t* __restrict__ cb, int64_t* __restrict__ ca) {
-  const int64_t base = indptr[row_begin];
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < nchunks; i += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t c = seq ? (int64_t)seq[i] : i;
-    const int64_t r0 = row_start[c], r1 = row_start[c + 1];
-    const int64_t b0 = indptr[r0], a0 = adj_ptr[r0];
-    cb[i] = b0 - base;
-    ca[i] = min(a0, max(nent - 1, (int64_t)0));
-    ca[nchunks + 1 + i] = (int64_t)((uint64_t)(uint32_t)(indptr[r1] - b0) | ((uint64_t)(uint32_t)(adj_ptr[r1] - a0) << 32));
-  }
-}
-
 // the chunk arrays of the persistent per-XCD schedule (k_gather_lin, k_gather_neo) in the order seq
-// (NULL: row order), and the XCD counters (zeroed)
-static int lin_chunk_desc(GatherArgs& P, int64_t** buf, hipStream_t s, const int32_t* seq) {
+// (NULL: row order), and the XCD counters (zeroed), in scratch that `buf` owns
+static int lin_chunk_desc(GatherArgs& P, Scratch& buf, hipStream_t s, const int32_t* seq) {
   int rc;
   if (P.nchunks >= (1ll << 30)) return fail(FA_E_CAPACITY, "gather plan has %lld chunks (>= 2^30)", (long long)P.nchunks);
   if (P.chunk_desc) {  // the plan's arrays (fa_plan_chunk_desc): only the XCD counters per launch
-    if ((rc = scratch_alloc((void**)buf, 1024, s))) return rc;
+    if ((rc = buf.alloc(1024, s))) return rc;
     P.chunk_b = P.chunk_desc;
     P.chunk_a = P.chunk_desc + (P.nchunks + 1);
-    P.ctr = reinterpret_cast<unsigned long long*>(*buf);
+    P.ctr = buf.as<unsigned long long>();
     HIP_TRY(hipMemsetAsync(P.ctr, 0, 1024, s));
     return FA_OK;
   }
-  if ((rc = scratch_alloc((void**)buf, sizeof(int64_t) * (3 * (P.nchunks + 1) + 128), s))) return rc;
-  P.chunk_b = *buf;
-  P.chunk_a = *buf + (P.nchunks + 1);
-  P.ctr = reinterpret_cast<unsigned long long*>(*buf + 3 * (P.nchunks + 1));  // 8 counters, 128 B apart
+  if ((rc = buf.alloc(sizeof(int64_t) * (3 * (P.nchunks + 1) + 128), s))) return rc;
+  int64_t* d = buf.as<int64_t>();
+  P.chunk_b = d;
+  P.chunk_a = d + (P.nchunks + 1);
+  P.ctr = reinterpret_cast<unsigned long long*>(d + 3 * (P.nchunks + 1));  // 8 counters, 128 B apart
   HIP_TRY(hipMemsetAsync(P.ctr, 0, 1024, s));
   k_lin_chunk_desc<<<grid_for(P.nchunks), 256, 0, s>>>(P.row_start, P.nchunks, P.A.indptr, P.A.row_begin, P.adj_ptr,
-                                                       P.M.ncells * P.M.nn, seq, *buf, *buf + (P.nchunks + 1));
+                                                       P.M.ncells * P.M.nn, seq, d, d + (P.nchunks + 1));
   LAUNCH_CHECK();
   return FA_OK;
 }
@@ -5292,9 +5326,10 @@ static int64_t gather_grid(K kernel, int64_t nchunks, int block = 256) {
   return std::min<int64_t>(std::min<int64_t>(8 * per, g), kMaxBlocks);  // kMaxBlocks % 8 == 0
 }
 
-// What a gather launch does: both stages with stream-ordered scratch (fa_assemble_matrix), or
-// one stage on a caller-owned work buffer (fa_gather_prepare / fa_gather_rows), or only report
-// that buffer's size.
+// What a gather launch does. A launch has two stages: the records stage builds the per-cell records
+// and their bc bits, the rows stage gathers the plan's rows from them. fa_assemble_matrix runs both
+// on stream-ordered scratch (FULL); the split gather runs one stage per call on a caller-owned work
+// buffer (PREP, ROWS) after asking for that buffer's size (SIZE).
 struct GatherStage {
   // prepared cell state (table items of k_gather_lin only; anything else: FA_E_UNSUPPORTED): SIZE_STATIC
   // reports the static records' bytes, BUILD writes them (and their bc bits) into `work`, PREPARED
@@ -5307,13 +5342,47 @@ struct GatherStage {
   int64_t ndlist = 0;
   bool fix = false;                // PREPARED: FA_DETERMINISTIC
   int** err_out = nullptr;         // receives the stage's device error word (FA_CHECK_ERRORS)
+  // the launch code asks these, never `mode`
   bool prepared() const { return mode == SIZE_STATIC || mode == BUILD || mode == PREPARED; }
+  bool size_only() const { return mode == SIZE || mode == SIZE_STATIC; }           // reports `bytes`, launches nothing
+  bool records() const { return mode == FULL || mode == PREP || mode == BUILD; }    // runs the records stage
+  bool rows() const { return mode == FULL || mode == ROWS || mode == PREPARED; }    // runs the rows stage
+  bool owns_scratch() const { return mode == FULL; }  // records in scratch of the launch, not in `work`
 };
 static int not_prepared() {
   return fail(FA_E_UNSUPPORTED, "prepared cell state: only for the table gather of uniform-nu linear elasticity "
                                 "(P2 / P3 simplices, affine Q1 / Q2 quadrilaterals, Q1 hexahedra, positional plan)");
 }
-static inline int64_t align256(int64_t b) { return (b + 255) & ~int64_t(255); }
+
+// Where a launch's per-cell records and bc mask live: scratch of the launch (a stage that owns its
+// scratch; returned on every path) or the caller's work buffer, laid out [records | mask].
+struct RecordBuffers {
+  double* rec = nullptr;
+  uint32_t* mask = nullptr;
+  static int64_t work_bytes(int64_t rec_doubles, int64_t mask_cells) {
+    return align256((int64_t)sizeof(double) * rec_doubles) + align256((int64_t)sizeof(uint32_t) * mask_cells);
+  }
+  int take(const GatherStage& W, int64_t rec_doubles, bool want_mask, int64_t mask_cells, hipStream_t s) {
+    int rc;
+    if (W.owns_scratch()) {
+      if ((rc = rec_own.alloc(sizeof(double) * rec_doubles, s))) return rc;
+      if (want_mask && (rc = mask_own.alloc(sizeof(uint32_t) * mask_cells, s))) return rc;
+      rec = rec_own.as<double>();
+      mask = mask_own.as<uint32_t>();
+    } else {
+      rec = reinterpret_cast<double*>(W.work);
+      mask = want_mask ? reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(W.work) + work_bytes(rec_doubles, 0)) : nullptr;
+    }
+    return FA_OK;
+  }
+  int free() {
+    const int rc = rec_own.free();
+    return rc ? rc : mask_own.free();
+  }
+
+ private:
+  Scratch rec_own, mask_own;
+};
 
 // every node's coordinates and constrained-dof bits (bit j: dof node * GD + j), for the fused P1 records
 template <int GD>
@@ -5379,21 +5448,122 @@ static double lin_fix_bound(int gd, int nn, double rlm, double trc, double amax)
   return (std::fabs(rlm) + 1.0) * amax * (1.0 + gd * std::fabs(trc));
 }
 
+// Which kernel can read which plan and which records, per launch_gather instantiation. Every guard of
+// the launch code is one of these names; each mirrors a static_assert or constant of the kernel it
+// guards. Where two of them differ, the line says why.
+template <int GD, int NN, int NV, int NQ, int NSPLIT, int MAT>
+struct GatherTraits {
+  using R = Rec<GD, NV, NQ, MAT>;
+  // records s Ji, sign(mu |J|): one nu for all cells (MAT_LINU simplices, MAT_AFFT affine tensor cells)
+  static constexpr bool uniform_nu = MAT == MAT_LINU || MAT == MAT_AFFT;
+  // an item is NN / NSPLIT whole columns of a cell with one Jacobian: what fa_plan_order lays items out for
+  static constexpr bool affine_items = R::SIMP && NN % NSPLIT == 0;
+  // packed slot order readable: the linear-elasticity kernels on such items (k_gather's ordered slots);
+  // any other kernel searches its slots in LDS
+  static constexpr bool packed_slots = (MAT == 0 || uniform_nu) && affine_items;
+  // positional items readable (k_gather's POSM): as packed_slots, but a positional item takes its bc
+  // bits from the 32-bit mask, so not the MAT_AFFT elements of more than 32 dofs (Q2 / Q3 hexahedra),
+  // which k_gather keeps on its wide-mask path. The difference from packed_slots is intended.
+  static constexpr bool positional_items = packed_slots && (MAT != MAT_AFFT || NN * GD <= 32);
+  // store-decoupled gather (k_gather_lin) applicable: uniform-nu records on positional items, and column
+  // ids below 64 (its packed column list)
+  static constexpr bool store_decoupled = uniform_nu && affine_items && NN * GD <= 32 && NN < 64;
+  // table items / prepared state applicable: k_gather_lin's elements past P1 (P1 blocks come from the
+  // record's gradients, not from the packed table), whose records are the small staged ones
+  static constexpr bool table_items = store_decoupled && NN != GD + 1 && R::SIZE <= 16;
+  // fused P1 records: k_gather_lin forms the record of a P1 simplex itself (MAT_LINU only: tensor
+  // cells have no P1 items)
+  static constexpr bool fused_p1 = MAT == MAT_LINU && affine_items && NN == GD + 1 && FA_LIN_FUSE;
+  // node-derived bc bits (k_rec_bcbits) into the record's word: uniform-nu staged records of <= 32 dofs.
+  // A property of the record, so NSPLIT does not enter (unlike store_decoupled); SIMP is implied.
+  static constexpr bool node_bits = uniform_nu && NN * GD <= 32 && R::SIZE <= 16;
+  // block-owner gather (k_gather_own<GD, NN>) applicable: MAT_LINU records, 32 bc bits, NN^2 < 127 for
+  // its contribution word. The kernel has no column split, so NSPLIT does not enter.
+  static constexpr bool block_owner = MAT == MAT_LINU && R::SIMP && NN * GD <= 32 && NN * NN < 127;
+  static_assert(!fused_p1 || store_decoupled, "fused records run in k_gather_lin");
+  static_assert(!store_decoupled || positional_items, "k_gather_lin reads positional items");
+};
+
+// a run-time flag as a template argument: f(std::true_type) or f(std::false_type)
+template <class F>
+static void with_bool(bool b, F&& f) {
+  if (b) f(std::true_type{});
+  else f(std::false_type{});
+}
+
+// One launch of a persistent per-XCD kernel (k_gather_lin, k_gather_neo) over P's chunks in the order
+// seq: its constant operands, its chunk arrays (owned here, returned on every path), then
+// launch(zero32, dump, chunks per XCD).
+template <class Launch>
+static int launch_persistent(GatherArgs& P, hipStream_t s, const int32_t* seq, Launch&& launch) {
+  int rc;
+  uint32_t* zero32 = nullptr;
+  double* dump = nullptr;
+  if ((rc = lin_scratch(&zero32, &dump))) return rc;
+  Scratch ldesc;
+  if ((rc = lin_chunk_desc(P, ldesc, s, seq))) return rc;
+  launch(zero32, dump, (P.nchunks + 7) / 8);
+  LAUNCH_CHECK();
+  return ldesc.free();
+}
+
+// k_gather_lin over P's chunks: the form's nu, the FIX bound from amax (the table's max entry), and the
+// one place that turns FUSE / P.fix / prepd into the kernel's variant. PREPD variants exist only where
+// MAY_PREPD (table items); FUSE ones only for P1.
+template <int GD, int NN, int NSPLIT, bool FUSE, bool MAY_PREPD>
+static int launch_lin(GatherArgs& P, hipStream_t s, const int32_t* seq, double amax, bool prepd) {
+  constexpr int LNT = lin_threads(GD, NN);
+  const double nu = P.F.nu;
+  P.rlm = 2.0 * nu / (1.0 - 2.0 * nu);
+  P.trc = 1.0 / (1.0 + P.rlm);
+  P.fixc = lin_fix_bound(GD, NN, P.rlm, P.trc, amax);
+  return launch_persistent(P, s, seq, [&](const uint32_t* zero32, double* dump, int64_t per8) {
+    auto go = [&](auto fix, auto pd) {
+      constexpr bool FIX = decltype(fix)::value, PREPD = decltype(pd)::value;
+      const int64_t grid = gather_grid(k_gather_lin<GD, NN, NSPLIT, LNT, FUSE, FIX, PREPD>, P.nchunks, LNT);
+      k_gather_lin<GD, NN, NSPLIT, LNT, FUSE, FIX, PREPD><<<(unsigned)grid, LNT, 0, s>>>(P, zero32, dump, per8);
+    };
+    with_bool(P.fix != 0, [&](auto fix) {
+      if constexpr (MAY_PREPD) with_bool(prepd, [&](auto pd) { go(fix, pd); });
+      else go(fix, std::false_type{});
+    });
+  });
+}
+
+// Dirichlet diagonals of the plan's rows: from the prepared list (fa_prepare_diag) when the launch has
+// one, else by marker (dolfinx set_diagonal)
+template <int GD>
+static int gather_diag(const GatherArgs& P, const int8_t* bc, hipStream_t s) {
+  if (P.dlist) {
+    if (P.ndlist > 0) {
+      k_set_diag_list<<<(unsigned)((P.ndlist + 255) / 256), 256, 0, s>>>(P.A.data, P.dlist, P.ndlist, P.diag);
+      LAUNCH_CHECK();
+    }
+  } else if (bc) {
+    launch_bc_diag<GD>(P.A, (P.A.row_end - P.A.row_begin) * GD, bc, P.diag, P.err, s);
+    LAUNCH_CHECK();
+  }
+  return FA_OK;
+}
+
+// the plan's ordered / positional slot map is not for this kernel: it searches its slots in LDS instead
+static void drop_slot_map(GatherArgs& P) { P.slots = nullptr; P.slot_order = 0; P.eadj = nullptr; }
+
 static bool neo_m_plan_ok(const GatherArgs& P, int nsplit) {
   return P.eadj && P.slots && P.slot_order == nsplit && !P.cw && P.plan_maxadj >= 0 && P.plan_maxadj * nsplit <= 256;
 }
 
+// the neo-Hookean M gather (k_gather_neo) and its records; its plans must be positional
 template <int GD, int NN, int NQ, int NSPLIT>
 static int launch_gather_neo(GatherArgs P, const int8_t* bc, hipStream_t s, const GatherStage& W) {
   using R = NeoM<GD, NQ>;
   if (W.prepared()) return not_prepared();  // the neo-Hookean records depend on u
   const int64_t nc = P.M.ncells;
-  const int64_t rec_bytes = align256((int64_t)sizeof(double) * R::count(nc));
-  if (W.mode == GatherStage::SIZE) {
-    *W.bytes = rec_bytes + align256((int64_t)sizeof(uint32_t) * nc);
+  if (W.size_only()) {
+    *W.bytes = RecordBuffers::work_bytes(R::count(nc), nc);
     return FA_OK;
   }
-  const bool rows = P.nchunks > 0 && W.mode != GatherStage::PREP;
+  const bool rows = W.rows() && P.nchunks > 0;
   if (rows && P.fix) return fail(FA_E_UNSUPPORTED, "deterministic assembly: not for the neo-Hookean gather");
   if (rows) {  // the kernel's plan: positional, ordered for NSPLIT, <= 256 items per chunk
     if (!neo_m_plan_ok(P, NSPLIT))
@@ -5405,290 +5575,193 @@ static int launch_gather_neo(GatherArgs P, const int8_t* bc, hipStream_t s, cons
                   P.plan_maxb, gather_maxb(true, GD * GD));
     if (P.nchunks >= (1ll << 31)) return fail(FA_E_CAPACITY, "gather plan has %lld chunks", (long long)P.nchunks);
   }
-  double* rec = nullptr;
-  uint32_t* mask = nullptr;
   int rc;
-  if (W.mode == GatherStage::FULL) {
-    if ((rc = scratch_alloc((void**)&rec, sizeof(double) * R::count(nc), s))) return rc;
-    if (bc && (rc = scratch_alloc((void**)&mask, sizeof(uint32_t) * nc, s))) return rc;
+  RecordBuffers B;
+  if ((rc = B.take(W, R::count(nc), bc != nullptr, nc, s))) return rc;
+  if (W.records() && nc > 0) {
+    k_neo_records_m<GD, NN, NQ><<<grid_for((nc + 63) / 64 * 64), 256, 0, s>>>(P.M, P.F, P.tab, bc, B.rec, B.mask);
+    LAUNCH_CHECK();
+  }
+  P.rec = B.rec;
+  P.bcmask = B.mask;
+  if (rows) {  // (the chunk visiting order stays in P.corder: the kernel reads it too)
+    rc = launch_persistent(P, s, P.corder, [&](const uint32_t* zero32, double* dump, int64_t per8) {
+      const int64_t grid = gather_grid(k_gather_neo<GD, NN, NQ, NSPLIT>, P.nchunks, 256);
+      k_gather_neo<GD, NN, NQ, NSPLIT><<<(unsigned)grid, 256, 0, s>>>(P, zero32, dump, per8);
+    });
+    if (rc || (rc = gather_diag<GD>(P, bc, s))) return rc;
+  }
+  return B.free();
+}
+
+// Records stage of launch_gather: every cell's record and bc bits into rec / mask. geom: the static
+// records of the prepared state (geometry only, scaled for the packed table, bits in the record word).
+template <int GD, int NN, int NV, int NQ, int NSPLIT, int MAT>
+static int gather_records(const GatherArgs& P, const int8_t* bc, hipStream_t s, bool geom, double* rec, uint32_t* mask) {
+  using R = Rec<GD, NV, NQ, MAT>;
+  using K = GatherTraits<GD, NN, NV, NQ, NSPLIT, MAT>;
+  const int64_t nc = P.M.ncells;
+  if (geom && bc && !(P.adj_ptr && P.adj_idx)) return fail(FA_E_ARG, "fa_prepare_cells with bcs needs the adjacency");
+  if (nc == 0) return FA_OK;
+  // uniform-nu records of <= 32 dofs: their bc bits from the constrained nodes (k_rec_bcbits), so the
+  // records kernel reads no dofmap (config E: records 1.88 -> ~1.5 ms)
+  const bool node_bits = K::node_bits && bc && P.adj_ptr && P.adj_idx;
+  if constexpr (R::SIZE <= 16) {  // small records: stored through LDS as contiguous runs
+    if (geom) {
+      if constexpr (K::table_items)
+        k_cell_records_staged<GD, NN, NV, NQ, MAT, true><<<grid_for(nc), 256, 0, s>>>(P.M, P.F, P.tab, nullptr, rec, nullptr,
+                                                                                   P.pks);
+    } else {
+      k_cell_records_staged<GD, NN, NV, NQ, MAT><<<grid_for(nc), 256, 0, s>>>(P.M, P.F, P.tab, node_bits ? nullptr : bc,
+                                                                             rec, mask);
+    }
   } else {
-    rec = reinterpret_cast<double*>(W.work);
-    mask = bc ? reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(W.work) + rec_bytes) : nullptr;
+    k_cell_records<GD, NN, NV, NQ, MAT><<<grid_for(nc), 256, 0, s>>>(P.M, P.F, P.tab, bc, rec, mask);
   }
-  if (nc > 0 && W.mode != GatherStage::ROWS) {
-    k_neo_records_m<GD, NN, NQ><<<grid_for((nc + 63) / 64 * 64), 256, 0, s>>>(P.M, P.F, P.tab, bc, rec, mask);
-    LAUNCH_CHECK();
-  }
-  P.rec = rec;
-  P.bcmask = mask;
-  if (rows) {
-    uint32_t* zero32 = nullptr;
-    double* dump = nullptr;
-    if ((rc = lin_scratch(&zero32, &dump))) return rc;
-    int64_t* ldesc = nullptr;
-    if ((rc = lin_chunk_desc(P, &ldesc, s, P.corder))) return rc;
-    const int64_t grid = gather_grid(k_gather_neo<GD, NN, NQ, NSPLIT>, P.nchunks, 256);
-    k_gather_neo<GD, NN, NQ, NSPLIT><<<(unsigned)grid, 256, 0, s>>>(P, zero32, dump, (P.nchunks + 7) / 8);
-    LAUNCH_CHECK();
-    HIP_TRY(hipFreeAsync(ldesc, s));
-    if (bc) {  // Dirichlet diagonals (dolfinx set_diagonal) of the plan's rows
-      launch_bc_diag<GD>(P.A, (P.A.row_end - P.A.row_begin) * GD, bc, P.diag, P.err, s);
+  LAUNCH_CHECK();
+  if constexpr (K::node_bits) {
+    if (node_bits && P.M.nnodes > 0) {
+      k_rec_bcbits<GD, NN, R::SIZE><<<grid_for((P.M.nnodes + 7) / 8), 256, 0, s>>>(P.adj_ptr, P.adj_idx, bc, P.M.nnodes,
+                                                                                rec, mask);
       LAUNCH_CHECK();
     }
   }
-  if (W.mode == GatherStage::FULL) {
-    HIP_TRY(hipFreeAsync(rec, s));
-    if (mask) HIP_TRY(hipFreeAsync(mask, s));
-  }
   return FA_OK;
+}
+
+// a plan k_gather_lin can run: positional, ordered for NSPLIT, one item per thread, row order in P
+// (the visiting order goes to lin_chunk_desc)
+template <int GD, int NN, int NSPLIT>
+static bool lin_plan_ok(const GatherArgs& P) {
+  return P.nchunks > 0 && !P.cw && P.eadj && P.slots && P.slot_order == NSPLIT && !P.corder && P.plan_maxadj >= 0 &&
+         P.plan_maxadj * NSPLIT <= lin_threads(GD, NN);
+}
+
+// P1 simplices through fa_assemble_matrix: k_gather_lin forms the records itself (FUSE), from a pack of
+// the nodes' coordinates and bc bits.
+// Only when the dofmap IS the geometry dofmap: the pack is indexed by vertex id and built over the
+// space's nodes, which are then the vertices (num_nodes == num_vertices). A space with its own P1
+// numbering (FunctionSpace.from_dofmap, a rank's slab) may have more or fewer nodes than the mesh
+// has vertices: it assembles through the records kernel (bc bits read by dof node, cell_bcmask).
+template <int GD, int NN, int NSPLIT>
+static bool fused_p1_ok(const GatherArgs& P) {
+  return lin_plan_ok<GD, NN, NSPLIT>(P) && P.F.E && P.M.geom == P.M.cells && P.plan_maxb <= lin_maxb(GD, NN) &&
+         P.nchunks < (1ll << 31);
+}
+template <int GD, int NN, int NSPLIT>
+static int launch_fused_p1(GatherArgs& P, const int8_t* bc, hipStream_t s, const int32_t* seq) {
+  int rc;
+  Scratch xp;
+  if ((rc = xp.alloc(sizeof(double) * 4 * (size_t)std::max<int64_t>(P.M.nnodes, 1), s))) return rc;
+  if (P.M.nnodes > 0) {
+    k_pack_nodes<GD><<<grid_for(P.M.nnodes), 256, 0, s>>>(P.M.x, bc, P.M.nnodes, xp.as<double>());
+    LAUNCH_CHECK();
+  }
+  P.xpack = xp.as<double>();
+  P.bcmask = bc ? xp.as<const uint32_t>() : nullptr;  // only "has bcs" is read
+  P.rec = nullptr;
+  if ((rc = launch_lin<GD, NN, NSPLIT, true, false>(P, s, seq, P.amax, false))) return rc;
+  if ((rc = gather_diag<GD>(P, bc, s))) return rc;
+  return xp.free();
+}
+
+// Rows stage of launch_gather: the plan's rows from P.rec / P.bcmask by the first kernel that takes
+// the plan -- k_gather_lin, else (contribution plan) k_gather_own, else k_gather.
+template <int GD, int NN, int NV, int NQ, int NSPLIT, int MAT>
+static int gather_rows(GatherArgs& P, const int8_t* bc, hipStream_t s, const int32_t* seq, bool prepd) {
+  using K = GatherTraits<GD, NN, NV, NQ, NSPLIT, MAT>;
+  int rc;
+  // the store-decoupled gather (k_gather_lin): positional plans of <= 256 items per chunk; affine
+  // simplices, and (round 6) affine quadrilaterals / Q1 hexahedra, whose uniform-nu records (s Ji, sign
+  // and bc bits) are the simplices' and whose reference tensor packs the same way (get_tables)
+  if constexpr (K::store_decoupled) {
+    if (lin_plan_ok<GD, NN, NSPLIT>(P) && (NN == GD + 1 || P.pk)) {
+      if (P.plan_maxb > lin_maxb(GD, NN))
+        return fail(FA_E_ARG, "gather plan chunks hold up to %d blocks, the kernel %d", P.plan_maxb, lin_maxb(GD, NN));
+      if (P.nchunks >= (1ll << 31)) return fail(FA_E_CAPACITY, "gather plan has %lld chunks", (long long)P.nchunks);
+      // records scaled by 1 / sqrt(D): |N| bounds. prepd: static records + per-cell coefficients (PREPD)
+      if ((rc = launch_lin<GD, NN, NSPLIT, false, K::table_items>(P, s, seq, P.pkmax, prepd))) return rc;
+      return gather_diag<GD>(P, bc, s);
+    }
+  }
+  if (prepd) return not_prepared();  // (a plan the table gather does not take)
+  if (P.nchunks == 0) return FA_OK;
+  if (P.fix)
+    return fail(FA_E_UNSUPPORTED, "deterministic assembly runs the affine-simplex elasticity gather (uniform nu, "
+                                  "positional plan: fa_plan_slots + fa_plan_order with an entry buffer) only");
+  Scratch desc, bhat;
+  if ((rc = chunk_desc(P, desc, s))) return rc;
+  if constexpr (K::uniform_nu) {  // B_ab = r Ahat_ab + Ahat_ab^T for this form's nu
+    const double nu = P.F.nu;
+    P.rlm = 2.0 * nu / (1.0 - 2.0 * nu);
+    P.trc = 1.0 / (1.0 + P.rlm);
+  }
+  if constexpr (MAT == MAT_LINU) {  // as a table (MAT_AFFT: the kernel forms it per block)
+    if ((rc = bhat.alloc(sizeof(double) * NN * NN * GD * GD, s))) return rc;
+    k_bhat<GD><<<grid_for(NN * NN), 256, 0, s>>>(P.ahat, NN * NN, P.rlm, bhat.as<double>());
+    LAUNCH_CHECK();
+    P.ahat = bhat.as<double>();
+  }
+  bool own = false;
+  if constexpr (K::block_owner) {
+    if (P.cw) {  // contribution plan: the block-owner gather
+      if (P.plan_maxb > own_maxb(GD * GD))
+        return fail(FA_E_ARG, "contribution plan chunks hold %d blocks, the kernel %d", P.plan_maxb, own_maxb(GD * GD));
+      const int64_t grid = gather_grid(k_gather_own<GD, NN>, P.nchunks);
+      k_gather_own<GD, NN><<<(unsigned)grid, 256, 0, s>>>(P);
+      own = true;
+    }
+  }
+  if (!own) {
+    const int64_t grid = gather_grid(k_gather<GD, NN, NV, NQ, NSPLIT, MAT>, P.nchunks);
+    k_gather<GD, NN, NV, NQ, NSPLIT, MAT><<<(unsigned)grid, 256, 0, s>>>(P);
+  }
+  LAUNCH_CHECK();
+  if ((rc = desc.free())) return rc;
+  return bhat.free();
 }
 
 template <int GD, int NN, int NV, int NQ, int NSPLIT, int MAT>
 static int launch_gather(GatherArgs P, const int8_t* bc, hipStream_t s, const GatherStage& W) {
   using R = Rec<GD, NV, NQ, MAT>;
+  using K = GatherTraits<GD, NN, NV, NQ, NSPLIT, MAT>;
   if constexpr (MAT == FA_NEO_HOOKEAN) {
-    // the neo-Hookean M gather (k_gather_neo) and its records; its plans must be positional
     static_assert(R::SIMP && NN % NSPLIT == 0 && NN * GD <= 32 && NN < 64, "neo-Hookean gather: simplices");
     return launch_gather_neo<GD, NN, NQ, NSPLIT>(P, bc, s, W);
   } else {
-  // ordered (packed) slots are read only by the affine-simplex linear kernel of the same NSPLIT;
-  // any other kernel searches its slots in LDS instead
-  if (P.slot_order && !((MAT == 0 || MAT == MAT_LINU || MAT == MAT_AFFT) && R::SIMP &&
-                        NN % NSPLIT == 0 && P.slot_order == NSPLIT)) {
-    P.slots = nullptr;
-    P.slot_order = 0;
-    P.eadj = nullptr;
-  }
-  // a positional plan's slot map is by position: a kernel without positional items (k_gather's
-  // POSM) cannot read it -- search the slots in LDS instead
-  constexpr bool POSM_K = (MAT == 0 || MAT == MAT_LINU || (MAT == MAT_AFFT && NN * GD <= 32)) && R::SIMP &&
-                          NN % NSPLIT == 0;
-  if (P.eadj && !POSM_K) {
-    P.slots = nullptr;
-    P.slot_order = 0;
-    P.eadj = nullptr;
-  }
-  static_assert(NN * GD <= 32 || MAT == MAT_AFFT, "bc mask holds 32 dofs");
-  if (P.plan_maxb > gather_maxb(false, GD * GD))
-    return fail(FA_E_ARG, "gather plan chunks hold up to %d blocks, this form's kernel %d: plan with fa_plan_gather_form",
-                P.plan_maxb, gather_maxb(false, GD * GD));
-  // the chunk visiting order (fa_plan_locality): k_gather_lin walks it per XCD (lin_chunk_desc);
-  // the generic k_gather keeps row order (its static grid measured 50.0 vs 51.5 ms on config E in
-  // Morton order, round 2)
-  const int32_t* seq = P.corder;
-  P.corder = nullptr;
-  const int64_t per8 = (P.nchunks + 7) / 8;
-  if constexpr (MAT == MAT_LINU && R::SIMP && NN == GD + 1 && NN % NSPLIT == 0 && FA_LIN_FUSE) {
-    // P1 simplices through fa_assemble_matrix: k_gather_lin forms the records itself (FUSE)
-    constexpr int LNT = lin_threads(GD, NN);
-    // Only when the dofmap IS the geometry dofmap: the pack is indexed by vertex id and built over the
-    // space's nodes, which are then the vertices (num_nodes == num_vertices). A space with its own P1
-    // numbering (FunctionSpace.from_dofmap, a rank's slab) may have more or fewer nodes than the mesh
-    // has vertices: it assembles through the records kernel (bc bits read by dof node, cell_bcmask).
-    if (W.mode == GatherStage::FULL && P.nchunks > 0 && P.F.E && !P.cw && P.eadj && P.M.geom == P.M.cells &&
-        P.slots && P.slot_order == NSPLIT && !P.corder && P.plan_maxadj * NSPLIT <= LNT && P.plan_maxadj >= 0 &&
-        P.plan_maxb <= lin_maxb(GD, NN) && P.nchunks < (1ll << 31)) {
-      int rc;
-      double* xp = nullptr;
-      if ((rc = scratch_alloc((void**)&xp, sizeof(double) * 4 * (size_t)std::max<int64_t>(P.M.nnodes, 1), s))) return rc;
-      if (P.M.nnodes > 0) {
-        k_pack_nodes<GD><<<grid_for(P.M.nnodes), 256, 0, s>>>(P.M.x, bc, P.M.nnodes, xp);
-        LAUNCH_CHECK();
-      }
-      P.xpack = xp;
-      P.bcmask = bc ? reinterpret_cast<const uint32_t*>(xp) : nullptr;  // only "has bcs" is read
-      P.rec = nullptr;
-      const double nu = P.F.nu;
-      P.rlm = 2.0 * nu / (1.0 - 2.0 * nu);
-      P.trc = 1.0 / (1.0 + P.rlm);
-      uint32_t* zero32 = nullptr;
-      double* dump = nullptr;
-      if ((rc = lin_scratch(&zero32, &dump))) return rc;
-      P.fixc = lin_fix_bound(GD, NN, P.rlm, P.trc, P.amax);
-      int64_t* ldesc = nullptr;
-      if ((rc = lin_chunk_desc(P, &ldesc, s, seq))) return rc;
-      if (P.fix) {
-        const int64_t grid = gather_grid(k_gather_lin<GD, NN, NSPLIT, LNT, true, true>, P.nchunks, LNT);
-        k_gather_lin<GD, NN, NSPLIT, LNT, true, true><<<(unsigned)grid, LNT, 0, s>>>(P, zero32, dump, per8);
-      } else {
-        const int64_t grid = gather_grid(k_gather_lin<GD, NN, NSPLIT, LNT, true>, P.nchunks, LNT);
-        k_gather_lin<GD, NN, NSPLIT, LNT, true><<<(unsigned)grid, LNT, 0, s>>>(P, zero32, dump, per8);
-      }
-      LAUNCH_CHECK();
-      HIP_TRY(hipFreeAsync(ldesc, s));
-      if (bc) {
-        launch_bc_diag<GD>(P.A, (P.A.row_end - P.A.row_begin) * GD, bc, P.diag, P.err, s);
-        LAUNCH_CHECK();
-      }
-      HIP_TRY(hipFreeAsync(xp, s));
+    static_assert(NN * GD <= 32 || MAT == MAT_AFFT, "bc mask holds 32 dofs");
+    // What this kernel family cannot read of the plan, it searches in LDS instead: ordered (packed)
+    // slots are for the kernels of the same NSPLIT, and a positional plan's slot map is by position.
+    if ((P.slot_order && !(K::packed_slots && P.slot_order == NSPLIT)) || (P.eadj && !K::positional_items))
+      drop_slot_map(P);
+    if (P.plan_maxb > gather_maxb(false, GD * GD))
+      return fail(FA_E_ARG, "gather plan chunks hold up to %d blocks, this form's kernel %d: plan with fa_plan_gather_form",
+                  P.plan_maxb, gather_maxb(false, GD * GD));
+    // the chunk visiting order (fa_plan_locality): k_gather_lin walks it per XCD (lin_chunk_desc);
+    // the generic k_gather keeps row order (its static grid measured 50.0 vs 51.5 ms on config E in
+    // Morton order, round 2)
+    const int32_t* seq = P.corder;
+    P.corder = nullptr;
+    if constexpr (K::fused_p1) {  // both stages in one kernel: no records
+      if (W.records() && W.rows() && fused_p1_ok<GD, NN, NSPLIT>(P)) return launch_fused_p1<GD, NN, NSPLIT>(P, bc, s, seq);
+    }
+    const int64_t nc = P.M.ncells;
+    // prepared cell state: the elements whose records split into a static part and a per-call
+    // coefficient, i.e. the table items of k_gather_lin
+    if (W.prepared() && !(K::table_items && P.pk)) return not_prepared();
+    if (W.size_only()) {
+      *W.bytes = W.prepared() ? (int64_t)sizeof(double) * R::count(nc) : RecordBuffers::work_bytes(R::count(nc), nc);
       return FA_OK;
     }
-  }
-  const int64_t nc = P.M.ncells;
-  const int64_t rec_bytes = align256((int64_t)sizeof(double) * R::count(nc));
-  // the table items of k_gather_lin: the elements whose records split into a static part and a per-call
-  // coefficient (prepared cell state)
-  constexpr bool TABLE_LIN = (MAT == MAT_LINU || MAT == MAT_AFFT) && R::SIMP && NN % NSPLIT == 0 && NN * GD <= 32 &&
-                             NN < 64 && NN != GD + 1 && R::SIZE <= 16;
-  if (W.prepared()) {
-    if constexpr (!TABLE_LIN) return not_prepared();
-    else {
-      if (!P.pk) return not_prepared();
-      if (W.mode == GatherStage::SIZE_STATIC) {
-        *W.bytes = (int64_t)sizeof(double) * R::count(nc);
-        return FA_OK;
-      }
-      if (W.mode == GatherStage::BUILD) {
-        if (bc && !(P.adj_ptr && P.adj_idx)) return fail(FA_E_ARG, "fa_prepare_cells with bcs needs the adjacency");
-        if (nc > 0) {
-          k_cell_records_staged<GD, NN, NV, NQ, MAT, true><<<grid_for(nc), 256, 0, s>>>(
-              P.M, P.F, P.tab, nullptr, reinterpret_cast<double*>(W.work), nullptr, P.pks);
-          LAUNCH_CHECK();
-          if (bc && P.M.nnodes > 0) {
-            k_rec_bcbits<GD, NN, R::SIZE><<<grid_for((P.M.nnodes + 7) / 8), 256, 0, s>>>(
-                P.adj_ptr, P.adj_idx, bc, P.M.nnodes, reinterpret_cast<double*>(W.work), nullptr);
-            LAUNCH_CHECK();
-          }
-        }
-        return FA_OK;
-      }
-      P.coef = W.coef;
-    }
-  }
-  if (W.mode == GatherStage::SIZE) {
-    *W.bytes = rec_bytes + align256((int64_t)sizeof(uint32_t) * nc);
-    return FA_OK;
-  }
-  double* rec = nullptr;
-  uint32_t* mask = nullptr;
-  int rc;
-  if (W.mode == GatherStage::FULL) {
-    if ((rc = scratch_alloc((void**)&rec, sizeof(double) * R::count(nc), s))) return rc;
-    if (bc && (rc = scratch_alloc((void**)&mask, sizeof(uint32_t) * nc, s))) return rc;
-  } else {
-    rec = reinterpret_cast<double*>(W.work);
-    mask = bc && W.mode != GatherStage::PREPARED ? reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(W.work) + rec_bytes)
-                                                 : nullptr;
-  }
-  if (nc > 0 && W.mode != GatherStage::ROWS && W.mode != GatherStage::PREPARED) {
-    // uniform-nu records of <= 32 dofs: their bc bits from the constrained nodes (k_rec_bcbits), so the
-    // records kernel reads no dofmap (config E: records 1.88 -> ~1.5 ms)
-    constexpr bool NODE_BITS = (MAT == MAT_LINU || MAT == MAT_AFFT) && NN * GD <= 32 && R::SIZE <= 16;
-    const bool node_bits = NODE_BITS && bc && P.adj_ptr && P.adj_idx;
-    if constexpr (R::SIZE <= 16)  // small records: stored through LDS as contiguous runs
-      k_cell_records_staged<GD, NN, NV, NQ, MAT><<<grid_for(nc), 256, 0, s>>>(P.M, P.F, P.tab, node_bits ? nullptr : bc,
-                                                                             rec, mask);
-    else k_cell_records<GD, NN, NV, NQ, MAT><<<grid_for(nc), 256, 0, s>>>(P.M, P.F, P.tab, bc, rec, mask);
-    LAUNCH_CHECK();
-    if constexpr (NODE_BITS) {
-      if (node_bits && P.M.nnodes > 0) {
-        k_rec_bcbits<GD, NN, R::SIZE><<<grid_for((P.M.nnodes + 7) / 8), 256, 0, s>>>(P.adj_ptr, P.adj_idx, bc, P.M.nnodes,
-                                                                                  rec, mask);
-        LAUNCH_CHECK();
-      }
-    }
-  }
-  P.rec = rec;
-  P.bcmask = mask;
-  // the store-decoupled gather (k_gather_lin): positional plans of <= 256 items per chunk; affine
-  // simplices, and (round 6) affine quadrilaterals / Q1 hexahedra, whose uniform-nu records (s Ji, sign
-  // and bc bits) are the simplices' and whose reference tensor packs the same way (get_tables)
-  if constexpr ((MAT == MAT_LINU || MAT == MAT_AFFT) && R::SIMP && NN % NSPLIT == 0 && NN * GD <= 32 && NN < 64) {
-    constexpr int LNT = lin_threads(GD, NN);
-    if (P.nchunks > 0 && W.mode != GatherStage::PREP && !P.cw && P.eadj && P.slots && (NN == GD + 1 || P.pk) &&
-        P.slot_order == NSPLIT && !P.corder && P.plan_maxadj * NSPLIT <= LNT && P.plan_maxadj >= 0) {
-      if (P.plan_maxb > lin_maxb(GD, NN))
-        return fail(FA_E_ARG, "gather plan chunks hold up to %d blocks, the kernel %d", P.plan_maxb, lin_maxb(GD, NN));
-      if (P.nchunks >= (1ll << 31)) return fail(FA_E_CAPACITY, "gather plan has %lld chunks", (long long)P.nchunks);
-      const double nu = P.F.nu, rr = 2.0 * nu / (1.0 - 2.0 * nu);
-      P.trc = 1.0 / (1.0 + rr);
-      P.rlm = rr;
-      uint32_t* zero32 = nullptr;
-      double* dump = nullptr;
-      if ((rc = lin_scratch(&zero32, &dump))) return rc;
-      P.fixc = lin_fix_bound(GD, NN, rr, P.trc, P.pkmax);  // records scaled by 1 / sqrt(D): |N| bounds
-      int64_t* ldesc = nullptr;
-      if ((rc = lin_chunk_desc(P, &ldesc, s, seq))) return rc;
-      bool prepd = false;  // static records + per-cell coefficients: the kernel's PREPD variants
-      if constexpr (TABLE_LIN) {
-        prepd = W.mode == GatherStage::PREPARED;
-        if (prepd && P.fix) {
-          const int64_t grid = gather_grid(k_gather_lin<GD, NN, NSPLIT, LNT, false, true, true>, P.nchunks, LNT);
-          k_gather_lin<GD, NN, NSPLIT, LNT, false, true, true><<<(unsigned)grid, LNT, 0, s>>>(P, zero32, dump, per8);
-        } else if (prepd) {
-          const int64_t grid = gather_grid(k_gather_lin<GD, NN, NSPLIT, LNT, false, false, true>, P.nchunks, LNT);
-          k_gather_lin<GD, NN, NSPLIT, LNT, false, false, true><<<(unsigned)grid, LNT, 0, s>>>(P, zero32, dump, per8);
-        }
-      }
-      if (prepd) {
-      } else if (P.fix) {
-        const int64_t grid = gather_grid(k_gather_lin<GD, NN, NSPLIT, LNT, false, true>, P.nchunks, LNT);
-        k_gather_lin<GD, NN, NSPLIT, LNT, false, true><<<(unsigned)grid, LNT, 0, s>>>(P, zero32, dump, per8);
-      } else {
-        const int64_t grid = gather_grid(k_gather_lin<GD, NN, NSPLIT, LNT>, P.nchunks, LNT);
-        k_gather_lin<GD, NN, NSPLIT, LNT><<<(unsigned)grid, LNT, 0, s>>>(P, zero32, dump, per8);
-      }
-      LAUNCH_CHECK();
-      HIP_TRY(hipFreeAsync(ldesc, s));
-      if (P.dlist) {  // Dirichlet diagonals from the prepared list (fa_prepare_diag)
-        if (P.ndlist > 0) {
-          k_set_diag_list<<<(unsigned)((P.ndlist + 255) / 256), 256, 0, s>>>(P.A.data, P.dlist, P.ndlist, P.diag);
-          LAUNCH_CHECK();
-        }
-      } else if (bc) {  // Dirichlet diagonals (dolfinx set_diagonal) of the plan's rows
-        launch_bc_diag<GD>(P.A, (P.A.row_end - P.A.row_begin) * GD, bc, P.diag, P.err, s);
-        LAUNCH_CHECK();
-      }
-      if (W.mode == GatherStage::FULL) {
-        HIP_TRY(hipFreeAsync(rec, s));
-        if (mask) HIP_TRY(hipFreeAsync(mask, s));
-      }
-      return FA_OK;
-    }
-  }
-  if (W.mode == GatherStage::PREPARED) return not_prepared();  // (a plan the table gather does not take)
-  if (P.nchunks > 0 && W.mode != GatherStage::PREP) {
-    if (P.fix)
-      return fail(FA_E_UNSUPPORTED, "deterministic assembly runs the affine-simplex elasticity gather (uniform nu, "
-                                    "positional plan: fa_plan_slots + fa_plan_order with an entry buffer) only");
-    int64_t* desc = nullptr;
-    if ((rc = chunk_desc(P, &desc, s))) return rc;
-    const int64_t grid = gather_grid(k_gather<GD, NN, NV, NQ, NSPLIT, MAT>, P.nchunks);
-    double* bhat = nullptr;
-    if constexpr (MAT == MAT_AFFT) {  // the kernel forms B_ab = r Ahat_ab + Ahat_ab^T per block
-      const double nu = P.F.nu;
-      P.rlm = 2.0 * nu / (1.0 - 2.0 * nu);
-      P.trc = 1.0 / (1.0 + P.rlm);
-    }
-    if constexpr (MAT == MAT_LINU) {  // B_ab = r Ahat_ab + Ahat_ab^T for this form's nu
-      const double nu = P.F.nu, rr = 2.0 * nu / (1.0 - 2.0 * nu);
-      if ((rc = scratch_alloc((void**)&bhat, sizeof(double) * NN * NN * GD * GD, s))) return rc;
-      k_bhat<GD><<<grid_for(NN * NN), 256, 0, s>>>(P.ahat, NN * NN, rr, bhat);
-      LAUNCH_CHECK();
-      P.ahat = bhat;
-      P.trc = 1.0 / (1.0 + rr);
-      P.rlm = rr;
-    }
-    bool launched = false;
-    if constexpr (MAT == MAT_LINU && Rec<GD, NV, NQ, MAT>::SIMP && NN * GD <= 32 && NN * NN < 127) {
-      if (P.cw) {  // contribution plan: the block-owner gather
-        if (P.plan_maxb > own_maxb(GD * GD))
-          return fail(FA_E_ARG, "contribution plan chunks hold %d blocks, the kernel %d", P.plan_maxb, own_maxb(GD * GD));
-        const int64_t go = gather_grid(k_gather_own<GD, NN>, P.nchunks);
-        k_gather_own<GD, NN><<<(unsigned)go, 256, 0, s>>>(P);
-        launched = true;
-      }
-    }
-    if (!launched) k_gather<GD, NN, NV, NQ, NSPLIT, MAT><<<(unsigned)grid, 256, 0, s>>>(P);
-    LAUNCH_CHECK();
-    HIP_TRY(hipFreeAsync(desc, s));
-    if (bhat) HIP_TRY(hipFreeAsync(bhat, s));
-  }
-  if (W.mode == GatherStage::FULL) {
-    HIP_TRY(hipFreeAsync(rec, s));
-    if (mask) HIP_TRY(hipFreeAsync(mask, s));
-  }
-  return FA_OK;
+    int rc;
+    RecordBuffers B;  // (prepared: the bc bits are in the records)
+    if ((rc = B.take(W, R::count(nc), bc && !W.prepared(), nc, s))) return rc;
+    if (W.records() && (rc = gather_records<GD, NN, NV, NQ, NSPLIT, MAT>(P, bc, s, W.prepared(), B.rec, B.mask))) return rc;
+    P.rec = B.rec;
+    P.bcmask = B.mask;
+    P.coef = W.coef;
+    if (W.rows() && (rc = gather_rows<GD, NN, NV, NQ, NSPLIT, MAT>(P, bc, s, seq, W.prepared()))) return rc;
+    return B.free();
   }
 }
 
@@ -5698,49 +5771,56 @@ template <int NN, int NQ, int NSPLIT>
 static int launch_hex_gather(GatherArgs P, const DevTables& T, const int8_t* bc, hipStream_t s, const GatherStage& W) {
   const int64_t nc = P.M.ncells;
   if (W.prepared()) return not_prepared();
-  if (P.slot_order) {
-    P.slots = nullptr;
-    P.slot_order = 0;
-    P.eadj = nullptr;
-  }
-  if (W.mode == GatherStage::SIZE) {
-    *W.bytes = align256((int64_t)sizeof(double) * 9 * NN * NN * nc);
+  if (P.slot_order) drop_slot_map(P);
+  if (W.size_only()) {
+    *W.bytes = RecordBuffers::work_bytes(9 * NN * NN * nc, 0);
     return FA_OK;
   }
-  double* eb = nullptr;
   int rc;
-  if (W.mode == GatherStage::FULL) {
-    if ((rc = scratch_alloc((void**)&eb, sizeof(double) * 9 * NN * NN * nc, s))) return rc;
-  } else {
-    eb = reinterpret_cast<double*>(W.work);
-  }
-  if (nc > 0 && W.mode != GatherStage::ROWS) {
+  RecordBuffers B;  // the element blocks; no mask (k_hex_mfma applies the bcs)
+  if ((rc = B.take(W, 9 * NN * NN * nc, false, 0, s))) return rc;
+  if (W.records() && nc > 0) {
     constexpr int thr = hex_threads_m(NN, 2);
     // one workgroup per cell (a resident grid looping over the cells with the next cell's inputs
     // prefetched measured 41.7 vs 41.5 ms on config Dmfma, round 5)
     const int grid = (int)std::min<int64_t>(nc, kMaxBlocks);
     BsrView none{nullptr, nullptr, nullptr, 0, 0};
-    k_hex_mfma<NN, NQ, 2><<<grid, thr, 0, s>>>(P.M, P.F, T, 0, nc, eb, none, bc, P.err);
+    k_hex_mfma<NN, NQ, 2><<<grid, thr, 0, s>>>(P.M, P.F, T, 0, nc, B.rec, none, bc, P.err);
     LAUNCH_CHECK();
   }
-  P.rec = eb;
+  P.rec = B.rec;
   P.bcmask = nullptr;
-  if (P.nchunks > 0 && W.mode != GatherStage::PREP) {
+  if (W.rows() && P.nchunks > 0) {
     if (P.fix) return fail(FA_E_UNSUPPORTED, "deterministic assembly: not for non-affine hexahedra");
-    int64_t* desc = nullptr;
-    if ((rc = chunk_desc(P, &desc, s))) return rc;
+    Scratch desc;
+    if ((rc = chunk_desc(P, desc, s))) return rc;
     const int64_t grid = gather_grid(k_gather<3, NN, 8, NQ, NSPLIT, MAT_BLOCKS>, P.nchunks);
     k_gather<3, NN, 8, NQ, NSPLIT, MAT_BLOCKS><<<(unsigned)grid, 256, 0, s>>>(P);
     LAUNCH_CHECK();
-    HIP_TRY(hipFreeAsync(desc, s));
+    if ((rc = desc.free())) return rc;
   }
-  if (W.mode == GatherStage::FULL) HIP_TRY(hipFreeAsync(eb, s));
-  return FA_OK;
+  return B.free();
 }
 
 // the uniform-nu affine-simplex kernels (MAT_LINU): E per cell with one nu, away from nu = 1/2
 static bool lin_uniform_nu(const FormView& F) {
   return F.kind == FA_LINEAR_ELASTICITY && F.E && F.nu > -0.99 && F.nu < 0.49;
+}
+
+// kSimplexShapes as template arguments: when (ct, p, nq) is row I, *rc = f(<GD>, <NN>, <NV>, <NQ>,
+// <NSPLIT>) as integral constants, with the neo-Hookean split if NEO; false if it is no row
+template <bool NEO, int I = 0, class F>
+static bool for_simplex_shape(int ct, int p, int nq, int* rc, F&& f) {
+  if constexpr (I < 4) {
+    constexpr SimplexShape e = kSimplexShapes[I];
+    if (ct != e.ct || p != e.p || nq != e.nq) return for_simplex_shape<NEO, I + 1>(ct, p, nq, rc, f);
+    using std::integral_constant;
+    *rc = f(integral_constant<int, e.gd>{}, integral_constant<int, e.nn>{}, integral_constant<int, e.nv>{},
+            integral_constant<int, e.nq>{}, integral_constant<int, NEO ? e.neo : e.nsplit>{});
+    return true;
+  } else {
+    return false;
+  }
 }
 
 static int dispatch_gather(const fa_mesh* m, const DevTables& T, int kind, const GatherArgs& P, const int8_t* bc,
@@ -5765,28 +5845,23 @@ static int dispatch_gather(const fa_mesh* m, const DevTables& T, int kind, const
   }
   const int ct = m->cell_type, p = m->degree, nq = T.nq;
   if (kind == FA_ASYM_DAMAGE) return launch_gather<2, 3, 3, 1, 1, FA_ASYM_DAMAGE>(P, bc, s, W);
+  // the simplex elements under one law: the plan's column split (kSimplexShapes), so a plan ordered
+  // for it keeps its positional slot map with the generic kernel too
+  int rc = FA_OK;
+  auto simplex = [&](auto mat) {
+    constexpr int MAT = decltype(mat)::value;
+    return for_simplex_shape<MAT == FA_NEO_HOOKEAN>(ct, p, nq, &rc, [&](auto gd, auto nn, auto nv, auto q, auto ns) {
+      return launch_gather<decltype(gd)::value, decltype(nn)::value, decltype(nv)::value, decltype(q)::value,
+                           decltype(ns)::value, MAT>(P, bc, s, W);
+    });
+  };
   if (kind == FA_NEO_HOOKEAN) {
-    if (ct == FA_TETRAHEDRON && p == 2 && nq == 4) return launch_gather<3, 10, 4, 4, FA_NEO_NSPLIT, FA_NEO_HOOKEAN>(P, bc, s, W);
-    // P1 tets: the column split of the plan's order (lin_simplex_nsplit), so the positional slot map fits
-    if (ct == FA_TETRAHEDRON && p == 1 && nq == 1) return launch_gather<3, 4, 4, 1, FA_P1TET_NSPLIT, FA_NEO_HOOKEAN>(P, bc, s, W);
-    if (ct == FA_TRIANGLE && p == 2 && nq == 3) return launch_gather<2, 6, 3, 3, 2, FA_NEO_HOOKEAN>(P, bc, s, W);
-    if (ct == FA_TRIANGLE && p == 1 && nq == 1) return launch_gather<2, 3, 3, 1, 1, FA_NEO_HOOKEAN>(P, bc, s, W);
+    if (simplex(std::integral_constant<int, FA_NEO_HOOKEAN>{})) return rc;
     *handled = false;
     return FA_OK;
   }
-  if (lin_uniform_nu(P.F)) {
-    if (ct == FA_TRIANGLE && p == 1 && nq == 1) return launch_gather<2, 3, 3, 1, 1, MAT_LINU>(P, bc, s, W);
-    if (ct == FA_TRIANGLE && p == 2 && nq == 3) return launch_gather<2, 6, 3, 3, 2, MAT_LINU>(P, bc, s, W);
-    if (ct == FA_TETRAHEDRON && p == 1 && nq == 1) return launch_gather<3, 4, 4, 1, FA_P1TET_NSPLIT, MAT_LINU>(P, bc, s, W);
-    if (ct == FA_TETRAHEDRON && p == 2 && nq == 4)
-      return launch_gather<3, 10, 4, 4, FA_P2TET_NSPLIT, MAT_LINU>(P, bc, s, W);
-  }
-  if (ct == FA_TRIANGLE && p == 1 && nq == 1) return launch_gather<2, 3, 3, 1, 1, 0>(P, bc, s, W);
-  if (ct == FA_TRIANGLE && p == 2 && nq == 3) return launch_gather<2, 6, 3, 3, 2, 0>(P, bc, s, W);
-  // the column split of the plan's order (lin_simplex_nsplit): a P1-tet plan ordered for
-  // FA_P1TET_NSPLIT keeps its positional slot map with this kernel too
-  if (ct == FA_TETRAHEDRON && p == 1 && nq == 1) return launch_gather<3, 4, 4, 1, FA_P1TET_NSPLIT, 0>(P, bc, s, W);
-  if (ct == FA_TETRAHEDRON && p == 2 && nq == 4) return launch_gather<3, 10, 4, 4, FA_P2TET_NSPLIT, 0>(P, bc, s, W);
+  if (lin_uniform_nu(P.F) && simplex(std::integral_constant<int, MAT_LINU>{})) return rc;
+  if (simplex(std::integral_constant<int, 0>{})) return rc;
   if (ct == FA_QUADRILATERAL && p == 1 && nq == 4) return launch_gather<2, 4, 4, 4, 1, 0>(P, bc, s, W);
   if (ct == FA_QUADRILATERAL && p == 2 && nq == 9) return launch_gather<2, 9, 4, 9, 3, 0>(P, bc, s, W);
   *handled = false;
@@ -5834,17 +5909,83 @@ extern "C" int fa_tabulate_cells(const fa_mesh* mesh, const fa_form* form, int64
   return launch_cell_blocks(0, mesh, M, F, T, c0, ncells_out, Ae, A, nullptr, nullptr, (hipStream_t)stream);
 }
 
+// The matrix's row window [wb, we) on this mesh (an empty window: every row). need_data: the call
+// writes the values, not only reads the pattern.
+static int row_window(const fa_mesh* mesh, const fa_bsr* A, bool need_data, int64_t* wb, int64_t* we) {
+  if (!A || !A->indptr || !A->indices || (need_data && !A->data)) return fail(FA_E_ARG, "null matrix");
+  if (A->bs != mesh->gdim || A->nrows != mesh->nnodes) return fail(FA_E_ARG, "matrix shape does not match mesh");
+  *wb = A->row_begin;
+  *we = A->row_end;
+  if (*we <= *wb) { *wb = 0; *we = mesh->nnodes; }
+  if (*wb < 0 || *we > mesh->nnodes) return fail(FA_E_ARG, "row window out of range");
+  return FA_OK;
+}
+
+// The per-process device error words (zeroed at first use, sticky until read): one per entry point
+// family, so that which call reports a sticky error does not depend on the others. A failed
+// allocation is reported by every call that needs the word, not remembered.
+enum ErrorWord { ERR_ASSEMBLE, ERR_SPLIT, ERR_DIAG_LIST };
+static int error_word(ErrorWord which, int** derr) {
+  static int* words[3] = {nullptr, nullptr, nullptr};
+  static std::mutex mu;
+  std::lock_guard<std::mutex> lk(mu);
+  if (!words[which]) {
+    int* p = nullptr;
+    HIP_TRY(hipMalloc((void**)&p, sizeof(int)));
+    HIP_TRY(hipMemset(p, 0, sizeof(int)));
+    words[which] = p;
+  }
+  *derr = words[which];
+  return FA_OK;
+}
+
 // Error flags raised by kernels (a pattern entry or diagonal the mesh needs is missing) are read
-// back only with FA_CHECK_ERRORS, which synchronises the stream; the timed path stays asynchronous.
+// back only on request (FA_CHECK_ERRORS, fa_prepare_diag), which synchronises the stream; the timed
+// path stays asynchronous. A raised word is cleared and reported as FA_E_PATTERN with `fmt` (one %x).
+static const char* const kAssemblyFlagged = "assembly kernel flagged error 0x%x (missing pattern entry / diagonal)";
+static int read_error_word(int* derr, hipStream_t s, const char* fmt = kAssemblyFlagged) {
+  int herr = 0;
+  HIP_TRY(hipMemcpyAsync(&herr, derr, sizeof(int), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  if (herr) {
+    HIP_TRY(hipMemset(derr, 0, sizeof(int)));
+    return fail(FA_E_PATTERN, fmt, herr);
+  }
+  return FA_OK;
+}
+
+// GatherArgs from (mesh view, form, tables, adjacency, plan, window). A stage without rows passes no
+// plan (NULL) and an empty window. `affine` stays 0: the caller says whether the plan's cell flags hold
+// for the records it reads.
+static GatherArgs gather_args(const MeshView& M, const FormView& F, const DevTables& T, const fa_adjacency* adj,
+                              const fa_plan* plan, const BsrView& Av, const int8_t* bc, double diag, int* derr) {
+  GatherArgs P{};
+  P.M = M; P.F = F; P.A = Av;
+  P.bc = bc; P.diag = diag; P.err = derr;
+  P.tab = T.wq; P.ahat = T.ahat; P.t1d = T.t1d; P.lat = T.lat;
+  P.amax = T.amax; P.pk = T.pk; P.pks = T.pk_scale; P.pkmax = T.pk_amax;
+  if (adj && adj->ptr && adj->idx) {  // (a records stage: the records' bc bits from the nodes, k_rec_bcbits)
+    P.adj_ptr = adj->ptr; P.adj_idx = adj->idx;
+  }
+  if (plan) {
+    P.row_start = plan->row_start; P.nchunks = plan->nchunks; P.corder = plan->corder; P.chunk_desc = plan->chunk_desc;
+    P.plan_maxb = plan->max_blocks; P.plan_maxadj = plan->max_adj;
+    P.slots = plan->slots;
+    P.slot_order = plan->slots ? plan->slot_order : 0;
+    P.eadj = P.slot_order ? plan->eadj : nullptr;
+    P.fix = (plan->cell_flags & FA_PLAN_DETERMINISTIC) ? 1 : 0;
+    set_contrib(P, plan);
+  }
+  return P;
+}
+static bool plan_affine(const fa_plan* plan) { return plan && (plan->cell_flags & FA_PLAN_AFFINE) != 0; }
+
 extern "C" int fa_assemble_matrix(const fa_mesh* mesh, const fa_form* form, const fa_adjacency* adj, const fa_plan* plan,
                                   const int8_t* bc, double diag, fa_bsr* A, int32_t flags, void* stream) {
   int rc = check_mesh(mesh);
   if (rc) return rc;
-  if (!A || !A->indptr || !A->indices || !A->data) return fail(FA_E_ARG, "null matrix");
-  if (A->bs != mesh->gdim || A->nrows != mesh->nnodes) return fail(FA_E_ARG, "matrix shape does not match mesh");
-  int64_t wb = A->row_begin, we = A->row_end;
-  if (we <= wb) { wb = 0; we = mesh->nnodes; }
-  if (wb < 0 || we > mesh->nnodes) return fail(FA_E_ARG, "row window out of range");
+  int64_t wb, we;
+  if ((rc = row_window(mesh, A, true, &wb, &we))) return rc;
   FormView F;
   if ((rc = form_view(mesh, form, F))) return rc;
   DevTables T;
@@ -5857,28 +5998,15 @@ extern "C" int fa_assemble_matrix(const fa_mesh* mesh, const fa_form* form, cons
     return rc;
   MeshView M{mesh->cells, mesh->geom, mesh->x, mesh->ncells, mesh->nnodes, mesh->nn, mesh->nv, mesh->gdim};
   BsrView Av{A->indptr, A->indices, A->data, wb, we};
-  static int* derr = nullptr;  // per-process device error word (sticky until read)
-  if (!derr) {
-    HIP_TRY(hipMalloc((void**)&derr, sizeof(int)));
-    HIP_TRY(hipMemset(derr, 0, sizeof(int)));
-  }
+  int* derr = nullptr;
+  if ((rc = error_word(ERR_ASSEMBLE, &derr))) return rc;
   bool scatter = (flags & FA_SCATTER) != 0;
   if (!scatter) {
     if (!adj || !adj->ptr || !adj->idx || !plan || !plan->row_start)
       return fail(FA_E_ARG, "FA_GATHER needs the adjacency and a plan (fa_plan_gather)");
-    GatherArgs P{};
-    P.M = M; P.F = F; P.A = Av;
-    P.adj_ptr = adj->ptr; P.adj_idx = adj->idx; P.row_start = plan->row_start; P.nchunks = plan->nchunks; P.corder = plan->corder; P.chunk_desc = plan->chunk_desc; P.plan_maxb = plan->max_blocks; P.plan_maxadj = plan->max_adj;
-    P.slots = plan->slots;
-    P.slot_order = plan->slots ? plan->slot_order : 0;
-    P.eadj = P.slot_order ? plan->eadj : nullptr;
-    P.bc = bc; P.diag = diag; P.tab = T.wq; P.ahat = T.ahat; P.rec = nullptr; P.bcmask = nullptr; P.err = derr; P.xpack = nullptr;
-    P.affine = (plan->cell_flags & FA_PLAN_AFFINE) != 0;
-    P.t1d = T.t1d; P.lat = T.lat;
-    P.fix = ((flags & FA_DETERMINISTIC) || (plan->cell_flags & FA_PLAN_DETERMINISTIC)) ? 1 : 0;
-    P.amax = T.amax;
-    P.pk = T.pk; P.pks = T.pk_scale; P.pkmax = T.pk_amax;
-    set_contrib(P, plan);
+    GatherArgs P = gather_args(M, F, T, adj, plan, Av, bc, diag, derr);
+    P.affine = plan_affine(plan);
+    if (flags & FA_DETERMINISTIC) P.fix = 1;
     if (P.fix && P.cw) return fail(FA_E_UNSUPPORTED, "deterministic assembly: not with a contribution plan");
     bool handled = false;
     rc = dispatch_gather(mesh, T, F.kind, P, bc, s, &handled);
@@ -5906,15 +6034,7 @@ extern "C" int fa_assemble_matrix(const fa_mesh* mesh, const fa_form* form, cons
       LAUNCH_CHECK();
     }
   }
-  if (flags & FA_CHECK_ERRORS) {
-    int herr = 0;
-    HIP_TRY(hipMemcpyAsync(&herr, derr, sizeof(int), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    if (herr) {
-      HIP_TRY(hipMemset(derr, 0, sizeof(int)));
-      return fail(FA_E_PATTERN, "assembly kernel flagged error 0x%x (missing pattern entry / diagonal)", herr);
-    }
-  }
+  if (flags & FA_CHECK_ERRORS) return read_error_word(derr, s);
   return FA_OK;
 }
 
@@ -5931,51 +6051,25 @@ static int gather_stage(const fa_mesh* mesh, const fa_form* form, const fa_adjac
   DevTables T;
   if ((rc = get_tables(mesh->cell_type, mesh->degree, form->qdeg, &T))) return rc;
   MeshView M{mesh->cells, mesh->geom, mesh->x, mesh->ncells, mesh->nnodes, mesh->nn, mesh->nv, mesh->gdim};
-  GatherArgs P{};
-  P.M = M; P.F = F;
-  P.A = BsrView{nullptr, nullptr, nullptr, 0, 0};
-  P.tab = T.wq; P.ahat = T.ahat; P.bc = bc; P.diag = diag;
-  P.affine = 0;  // the prepare stage has no plan: tensor cells keep the element-kernel path
-  P.t1d = T.t1d; P.lat = T.lat;
-  static int* derr = nullptr;  // device error word of the split path
-  if (!derr) {
-    HIP_TRY(hipMalloc((void**)&derr, sizeof(int)));
-    HIP_TRY(hipMemset(derr, 0, sizeof(int)));
-  }
-  P.err = derr;
+  int* derr = nullptr;
+  if ((rc = error_word(ERR_SPLIT, &derr))) return rc;
   if (W.err_out) *W.err_out = derr;
-  if (adj && adj->ptr && adj->idx) {  // (the prepare stage: the records' bc bits from the nodes, k_rec_bcbits)
-    P.adj_ptr = adj->ptr;
-    P.adj_idx = adj->idx;
-  }
-  if (W.mode == GatherStage::SIZE_STATIC || W.mode == GatherStage::BUILD) {
-    // no rows: the plan only says whether tensor cells are affine (their route to the table gather)
-    P.affine = plan && (plan->cell_flags & FA_PLAN_AFFINE) != 0;
-    P.pk = T.pk; P.pks = T.pk_scale;
-  }
-  if (W.mode == GatherStage::ROWS || W.mode == GatherStage::PREPARED) {
-    if (W.mode == GatherStage::PREPARED) P.affine = plan && (plan->cell_flags & FA_PLAN_AFFINE) != 0;
-    if (!A || !A->indptr || !A->indices || !A->data) return fail(FA_E_ARG, "null matrix");
-    if (A->bs != mesh->gdim || A->nrows != mesh->nnodes) return fail(FA_E_ARG, "matrix shape does not match mesh");
-    int64_t wb = A->row_begin, we = A->row_end;
-    if (we <= wb) { wb = 0; we = mesh->nnodes; }
-    if (wb < 0 || we > mesh->nnodes) return fail(FA_E_ARG, "row window out of range");
+  BsrView Av{nullptr, nullptr, nullptr, 0, 0};
+  if (W.rows()) {
+    int64_t wb, we;
+    if ((rc = row_window(mesh, A, true, &wb, &we))) return rc;
     if (!adj || !adj->ptr || !adj->idx || !plan || !plan->row_start)
       return fail(FA_E_ARG, "fa_gather_rows needs the adjacency and a plan (fa_plan_gather)");
-    P.A = BsrView{A->indptr, A->indices, A->data, wb, we};
-    P.adj_ptr = adj->ptr; P.adj_idx = adj->idx; P.row_start = plan->row_start; P.nchunks = plan->nchunks; P.corder = plan->corder; P.chunk_desc = plan->chunk_desc; P.plan_maxb = plan->max_blocks; P.plan_maxadj = plan->max_adj;
-    P.slots = plan->slots;
-    P.slot_order = plan->slots ? plan->slot_order : 0;
-    P.eadj = P.slot_order ? plan->eadj : nullptr;
-    P.fix = (plan->cell_flags & FA_PLAN_DETERMINISTIC) ? 1 : 0;
-    P.amax = T.amax;
-    P.pk = T.pk; P.pks = T.pk_scale; P.pkmax = T.pk_amax;
-    set_contrib(P, plan);
-    if (W.mode == GatherStage::PREPARED) {
-      if (W.fix) P.fix = 1;
-      P.dlist = W.dlist;
-      P.ndlist = W.ndlist;
-    }
+    Av = BsrView{A->indptr, A->indices, A->data, wb, we};
+  }
+  GatherArgs P = gather_args(M, F, T, adj, W.rows() ? plan : nullptr, Av, bc, diag, derr);
+  // Tensor cells: the plan says whether they are affine (their route to the table gather). The split
+  // gather's prepare stage has no plan, so both its stages keep the element-kernel path.
+  P.affine = W.prepared() && plan_affine(plan);
+  if (W.rows()) {
+    if (W.fix) P.fix = 1;
+    P.dlist = W.dlist;
+    P.ndlist = W.ndlist;
     if (P.fix && P.cw) return fail(FA_E_UNSUPPORTED, "deterministic assembly: not with a contribution plan");
   }
   bool handled = false;
@@ -6052,16 +6146,18 @@ extern "C" int fa_prepare_coef(const fa_mesh* mesh, const fa_form* form, const f
   return FA_OK;
 }
 
+// the window of a diagonal-list call, and a zeroed device counter for it
 static int diag_window(const fa_mesh* mesh, const fa_bsr* A, const int8_t* bc, int64_t* wb, int64_t* we) {
   int rc = check_mesh(mesh);
   if (rc) return rc;
-  if (!A || !A->indptr || !A->indices) return fail(FA_E_ARG, "null matrix");
-  if (A->bs != mesh->gdim || A->nrows != mesh->nnodes) return fail(FA_E_ARG, "matrix shape does not match mesh");
+  if ((rc = row_window(mesh, A, false, wb, we))) return rc;
   if (!bc) return fail(FA_E_ARG, "null bc marker");
-  *wb = A->row_begin;
-  *we = A->row_end;
-  if (*we <= *wb) { *wb = 0; *we = mesh->nnodes; }
-  if (*wb < 0 || *we > mesh->nnodes) return fail(FA_E_ARG, "row window out of range");
+  return FA_OK;
+}
+static int diag_counter(Scratch& dc, hipStream_t s) {
+  int rc = dc.alloc(sizeof(unsigned long long), s);
+  if (rc) return rc;
+  HIP_TRY(hipMemsetAsync(dc.as<void>(), 0, sizeof(unsigned long long), s));
   return FA_OK;
 }
 
@@ -6071,18 +6167,17 @@ extern "C" int fa_prepare_diag_count(const fa_mesh* mesh, const fa_bsr* A, const
   if (rc) return rc;
   if (!count) return fail(FA_E_ARG, "null count");
   hipStream_t s = (hipStream_t)stream;
-  unsigned long long* dc = nullptr;
-  if ((rc = scratch_alloc((void**)&dc, sizeof(unsigned long long), s))) return rc;
-  HIP_TRY(hipMemsetAsync(dc, 0, sizeof(unsigned long long), s));
+  Scratch dc;
+  if ((rc = diag_counter(dc, s))) return rc;
   const int64_t n = (we - wb) * mesh->gdim;
   if (n > 0) {
-    k_diag_count<<<grid_for(n), 256, 0, s>>>(bc, wb * mesh->gdim, we * mesh->gdim, dc);
+    k_diag_count<<<grid_for(n), 256, 0, s>>>(bc, wb * mesh->gdim, we * mesh->gdim, dc.as<unsigned long long>());
     LAUNCH_CHECK();
   }
   unsigned long long h = 0;
-  HIP_TRY(hipMemcpyAsync(&h, dc, sizeof(h), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(&h, dc.as<void>(), sizeof(h), hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
-  HIP_TRY(hipFreeAsync(dc, s));
+  if ((rc = dc.free())) return rc;
   *count = (int64_t)h;
   return FA_OK;
 }
@@ -6095,29 +6190,20 @@ extern "C" int fa_prepare_diag(const fa_mesh* mesh, const fa_bsr* A, const int8_
   if (count < 0 || (count > 0 && !offsets)) return fail(FA_E_ARG, "null diagonal list");
   if (count == 0) return FA_OK;
   hipStream_t s = (hipStream_t)stream;
-  static int* derr = nullptr;  // device error word of the list builds (read by no one: FA_CHECK_ERRORS
-  if (!derr) {                 // assemblies validate the pattern themselves)
-    HIP_TRY(hipMalloc((void**)&derr, sizeof(int)));
-    HIP_TRY(hipMemset(derr, 0, sizeof(int)));
-  }
-  unsigned long long* dc = nullptr;
-  if ((rc = scratch_alloc((void**)&dc, sizeof(unsigned long long), s))) return rc;
-  HIP_TRY(hipMemsetAsync(dc, 0, sizeof(unsigned long long), s));
+  int* derr = nullptr;  // device error word of the list builds (read here only: FA_CHECK_ERRORS assemblies
+  if ((rc = error_word(ERR_DIAG_LIST, &derr))) return rc;  // validate the pattern themselves)
+  Scratch dc;
+  if ((rc = diag_counter(dc, s))) return rc;
   HIP_TRY(hipMemsetAsync(offsets, 0xFF, sizeof(int64_t) * (size_t)count, s));  // -1: no diagonal stored
   BsrView Av{A->indptr, A->indices, A->data, wb, we};
   const int64_t n = (we - wb) * mesh->gdim;
-  if (mesh->gdim == 2) k_diag_list_build<2><<<grid_for(n), 256, 0, s>>>(Av, bc, offsets, count, dc, derr);
-  else k_diag_list_build<3><<<grid_for(n), 256, 0, s>>>(Av, bc, offsets, count, dc, derr);
+  if (mesh->gdim == 2) k_diag_list_build<2><<<grid_for(n), 256, 0, s>>>(Av, bc, offsets, count, dc.as<unsigned long long>(), derr);
+  else k_diag_list_build<3><<<grid_for(n), 256, 0, s>>>(Av, bc, offsets, count, dc.as<unsigned long long>(), derr);
   LAUNCH_CHECK();
-  int herr = 0;  // a constrained dof without a diagonal block: reported here, once, not per assembly
-  HIP_TRY(hipMemcpyAsync(&herr, derr, sizeof(int), hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  HIP_TRY(hipFreeAsync(dc, s));
-  if (herr) {
-    HIP_TRY(hipMemset(derr, 0, sizeof(int)));
-    return fail(FA_E_PATTERN, "fa_prepare_diag: a constrained dof has no diagonal block in the pattern (error 0x%x)", herr);
-  }
-  return FA_OK;
+  // a constrained dof without a diagonal block: reported here, once, not per assembly
+  if ((rc = read_error_word(derr, s, "fa_prepare_diag: a constrained dof has no diagonal block in the pattern (error 0x%x)")))
+    return rc;
+  return dc.free();
 }
 
 extern "C" int fa_assemble_matrix_prepared(const fa_mesh* mesh, const fa_form* form, const fa_adjacency* adj,
@@ -6148,15 +6234,7 @@ extern "C" int fa_assemble_matrix_prepared(const fa_mesh* mesh, const fa_form* f
   if (!(flags & FA_KEEP_COEF) && (rc = fa_prepare_coef(mesh, form, prepared, stream))) return rc;
   // (no marker: the records carry the bits and the list the diagonals)
   if ((rc = gather_stage(mesh, form, adj, plan, nullptr, diag, A, W, s))) return rc;
-  if ((flags & FA_CHECK_ERRORS) && derr) {
-    int herr = 0;
-    HIP_TRY(hipMemcpyAsync(&herr, derr, sizeof(int), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    if (herr) {
-      HIP_TRY(hipMemset(derr, 0, sizeof(int)));
-      return fail(FA_E_PATTERN, "assembly kernel flagged error 0x%x (missing pattern entry / diagonal)", herr);
-    }
-  }
+  if ((flags & FA_CHECK_ERRORS) && derr) return read_error_word(derr, s);
   return FA_OK;
 }
 

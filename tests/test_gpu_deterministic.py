@@ -127,6 +127,65 @@ def test_deterministic_unsupported_form_fails_loudly(oracle, dev):
         fem.assemble_matrix(a, deterministic=True)
 
 
+def _pool_used_bytes(dev):
+    """Bytes in use in the device's default stream-ordered memory pool (this process's only), read
+    through the HIP runtime that torch has loaded."""
+    import ctypes
+
+    hip = ctypes.CDLL("libamdhip64.so")
+    pool, used = ctypes.c_void_p(), ctypes.c_uint64(0)
+    assert hip.hipDeviceGetDefaultMemPool(ctypes.byref(pool), ctypes.c_int(dev.index or 0)) == 0
+    hipMemPoolAttrUsedMemCurrent = 7
+    assert hip.hipMemPoolGetAttribute(pool, ctypes.c_int(hipMemPoolAttrUsedMemCurrent), ctypes.byref(used)) == 0
+    return used.value
+
+
+def _refused_hex(dev):
+    from femasm import fem, mesh
+
+    # non-affine Q2 hexahedra (the MFMA element path): one element-block buffer is 216 * 9 * 27^2 * 8 B ~ 11 MB.
+    # The cells must lose their parallel edges: a shift of each coordinate by a function of itself alone
+    # (x + f(x)) keeps them boxes, which the plan rightly calls affine; a product of the other two does not.
+    m = mesh.create_unit_cube(6, 6, 6, cell_type=mesh.CellType.hexahedron, device=dev)
+    m.x = m.x + 0.02 * m.x.roll(1, 1) * m.x.roll(2, 1)
+    V = fem.functionspace(m, ("Lagrange", 2, (3,)))
+    return fem.LinearElasticity(V, E=1.0, nu=0.3)
+
+
+def _refused_generic(dev):
+    from femasm import fem, mesh
+
+    # lam / mu instead of E: the generic k_gather, which has no deterministic mode
+    m = mesh.create_unit_cube(6, 5, 4, cell_type=mesh.CellType.tetrahedron, device=dev)
+    V = fem.functionspace(m, ("Lagrange", 2, (3,)))
+    return fem.LinearElasticity(V, lam=1.2, mu=0.8)
+
+
+@pytest.mark.parametrize("route", [_refused_hex, _refused_generic])
+def test_refused_assembly_returns_its_scratch(dev, route):
+    """A refused deterministic assembly has already taken stream-ordered scratch (element blocks, or
+    records and mask) when it refuses; the pool never releases memory, so the refusal must free it."""
+    from femasm import _lib, fem
+
+    a = route(dev)
+    A = fem.create_matrix(a)
+
+    def refused():
+        with pytest.raises(_lib.FemasmError, match="deterministic"):
+            fem.assemble_matrix(a, A=A, deterministic=True)
+
+    for _ in range(2):
+        refused()
+    torch.cuda.synchronize()
+    before = _pool_used_bytes(dev)
+    for _ in range(10):
+        refused()
+    torch.cuda.synchronize()
+    after = _pool_used_bytes(dev)
+    print(f"pool bytes in use: {before} before, {after} after ten refused calls")
+    assert after == before
+
+
 @pytest.mark.parametrize("n", [203])
 def test_config_e_deterministic_full_size(oracle, dev, n):
     """Config E (50.2 M P2 tets) in deterministic mode: two assemblies bit-identical, sampled rows
