@@ -3294,7 +3294,11 @@ __global__ __launch_bounds__(256, 3) void k_neo_records_m(MeshView M, FormView F
 }
 
 // 2 waves / SIMD (215 VGPRs, no spills in the item loop; 3 waves measured slower: spilled records)
-template <int GD, int NN, int NQ, int NSPLIT>
+// MULTI: for a plan with a chunk of more than 256 items (a row with more than 256 / NSPLIT adjacency
+// entries gets a chunk of its own, up to kGatherMaxAdj entries: plan_gather). The first 256 items of a
+// chunk run as in the default variant; the rest follow in passes of 256 before the chunk's barrier,
+// their entries, records and slots loaded without prefetch.
+template <int GD, int NN, int NQ, int NSPLIT, bool MULTI = false>
 __global__ __launch_bounds__(256, 2) void k_gather_neo(GatherArgs P, const uint32_t* __restrict__ zero32,
                                                        double* __restrict__ dump, int64_t per) {
   using R = NeoM<GD, NQ>;
@@ -3418,9 +3422,14 @@ __global__ __launch_bounds__(256, 2) void k_gather_neo(GatherArgs P, const uint3
     const int64_t off = d0.b0 * BS2;
     const int h = (int)(off & 1);
     const int nb = d0.nb;
-    const bool valid = jit < d0.na;
+    // the item of this pass: cur, its entry id pfi, and whether the lane has one. The default variant
+    // makes one pass per chunk (the loop below runs once); MULTI reloads them for each further pass
+    constexpr int EPP = NTH / NSPLIT;  // entries per pass
+    int32_t pfi = pf0;
+    bool valid = jit < d0.na;
+    for (int base = 0;;) {
     {
-      const int aloc = pf0 % NN;
+      const int aloc = pfi % NN;
       const uint32_t rowm = (cur.mask >> (aloc * GD)) & ((1u << GD) - 1);
       // The LDS adds are issued by every lane (no branch): a lane without an item of this chunk (or,
       // on a broken pattern, with a slot past the chunk) adds zeros to an in-chunk slot of its own.
@@ -3520,6 +3529,17 @@ __global__ __launch_bounds__(256, 2) void k_gather_neo(GatherArgs P, const uint3
             for (int kk = 0; kk < GD; ++kk) atomicAdd(ap + i * GD + kk, K[i][kk]);
         }
       }
+      }
+    }
+      if constexpr (!MULTI) {
+        break;
+      } else {  // the chunk's next 256 items, loaded without prefetch (d0 is wave-uniform)
+        base += EPP;
+        if (base >= d0.na) break;
+        const Desc dx{d0.b0, d0.a0 + base, d0.nb, d0.na - base};  // the chunk's entries from `base` on
+        pfi = load_entry(dx);
+        load_item(dx, pfi, cur);
+        valid = jit < dx.na;
       }
     }
     // chunk k+1's records / slots / masks: the item registers are dead here, and these loads are
@@ -5549,9 +5569,13 @@ static int gather_diag(const GatherArgs& P, const int8_t* bc, hipStream_t s) {
 // the plan's ordered / positional slot map is not for this kernel: it searches its slots in LDS instead
 static void drop_slot_map(GatherArgs& P) { P.slots = nullptr; P.slot_order = 0; P.eadj = nullptr; }
 
+// a plan k_gather_neo can run: positional, ordered for nsplit, chunks within the planner's hard entry cap
 static bool neo_m_plan_ok(const GatherArgs& P, int nsplit) {
-  return P.eadj && P.slots && P.slot_order == nsplit && !P.cw && P.plan_maxadj >= 0 && P.plan_maxadj * nsplit <= 256;
+  return P.eadj && P.slots && P.slot_order == nsplit && !P.cw && P.plan_maxadj >= 0 && P.plan_maxadj <= kGatherMaxAdj;
 }
+// ... whose largest chunk holds more than the workgroup's 256 items: a row over the entry target in a
+// chunk of its own (k_chunk_seg). Such a plan runs the kernel's MULTI variant
+static bool neo_m_plan_multi(const GatherArgs& P, int nsplit) { return P.plan_maxadj * nsplit > 256; }
 
 // the neo-Hookean M gather (k_gather_neo) and its records; its plans must be positional
 template <int GD, int NN, int NQ, int NSPLIT>
@@ -5569,7 +5593,7 @@ static int launch_gather_neo(GatherArgs P, const int8_t* bc, hipStream_t s, cons
     if (!neo_m_plan_ok(P, NSPLIT))
       return fail(FA_E_ARG, "the neo-Hookean gather needs a positional plan ordered for %d column parts with <= %d "
                   "entries per chunk (fa_plan_gather_form + fa_plan_slots + fa_plan_order with an entry buffer)",
-                  NSPLIT, 256 / NSPLIT);
+                  NSPLIT, kGatherMaxAdj);
     if (P.plan_maxb > gather_maxb(true, GD * GD))
       return fail(FA_E_ARG, "gather plan chunks hold up to %d blocks, the kernel %d: plan with fa_plan_gather_form",
                   P.plan_maxb, gather_maxb(true, GD * GD));
@@ -5586,8 +5610,11 @@ static int launch_gather_neo(GatherArgs P, const int8_t* bc, hipStream_t s, cons
   P.bcmask = B.mask;
   if (rows) {  // (the chunk visiting order stays in P.corder: the kernel reads it too)
     rc = launch_persistent(P, s, P.corder, [&](const uint32_t* zero32, double* dump, int64_t per8) {
-      const int64_t grid = gather_grid(k_gather_neo<GD, NN, NQ, NSPLIT>, P.nchunks, 256);
-      k_gather_neo<GD, NN, NQ, NSPLIT><<<(unsigned)grid, 256, 0, s>>>(P, zero32, dump, per8);
+      with_bool(neo_m_plan_multi(P, NSPLIT), [&](auto multi) {
+        constexpr bool MULTI = decltype(multi)::value;
+        const int64_t grid = gather_grid(k_gather_neo<GD, NN, NQ, NSPLIT, MULTI>, P.nchunks, 256);
+        k_gather_neo<GD, NN, NQ, NSPLIT, MULTI><<<(unsigned)grid, 256, 0, s>>>(P, zero32, dump, per8);
+      });
     });
     if (rc || (rc = gather_diag<GD>(P, bc, s))) return rc;
   }
@@ -6586,7 +6613,8 @@ __global__ __launch_bounds__(256) void k_bsr_mult(BsrView A, const double* __res
     }
 #pragma unroll
     for (int i = 0; i < BS; ++i) y[r * BS + i] = acc[i];
-    if constexpr (BS == 2) store_guard2(acc[0], acc[1]);
+    if constexpr (BS == 1) store_guard1(acc[0]);
+    else if constexpr (BS == 2) store_guard2(acc[0], acc[1]);
     else store_guard3(acc[0], acc[1], acc[2]);
   }
 }

@@ -651,11 +651,14 @@ def _use_contrib(V, kind, owner) -> bool:
 
 
 def _plan_contrib(V, fm, adj, fb, rs, plan, sh):
-    """Chunking + contribution plan of the block-owner gather; None (plan untouched) when a chunk
-    cannot hold a row's entries (then the caller plans the LDS-atomic gather)."""
+    """Chunking + contribution plan of the block-owner gather; None when a chunk cannot hold a row's
+    blocks or entries (then the caller plans the LDS-atomic gather, whose block cap is the larger one:
+    a row of 897 .. 1023 blocks of a P2 triangle mesh is over own_maxb only)."""
     L = _lib.load()
     rc = L.fa_plan_gather_contrib(ctypes.byref(fm), ctypes.byref(adj), ctypes.byref(fb), rs.data_ptr(),
                                   ctypes.byref(plan), sh)
+    if rc == _lib.FA_E_CAPACITY:  # a row over the block-owner chunk's caps
+        return None
     _lib.check(rc, "fa_plan_gather_contrib")
     if plan.nchunks == 0:
         return None
@@ -666,7 +669,7 @@ def _plan_contrib(V, fm, adj, fb, rs, plan, sh):
     rc = L.fa_plan_contrib(ctypes.byref(fm), ctypes.byref(adj), ctypes.byref(fb), buf.data_ptr(), buf.numel(),
                            ctypes.byref(plan), sh)
     if rc != _lib.FA_OK:
-        if rc == -5:  # FA_E_CAPACITY: rows with more entries than a chunk holds
+        if rc == _lib.FA_E_CAPACITY:  # rows with more entries than a chunk holds
             return None
         _lib.check(rc, "fa_plan_contrib")
     return buf

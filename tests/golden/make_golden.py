@@ -7,6 +7,10 @@
   config_a_p1_elasticity.npz config A (71x71 unit square, 2 triangles per square, right
                              diagonal, E = E_range[cell % 200]) with the reference bcs
                              (x=0 clamped, x=1 prescribed) — computed by the oracle.
+  delaunay_tets_n4.npz       x [125, 3] f64, cells [426, 4] i32: Delaunay tetrahedra of a jittered
+                             5 x 5 x 5 lattice on the unit cube (needs scipy; tests/irregular_meshes.py).
+
+  python make_golden.py [name ...]   regenerates the named fixtures (default: all).
 """
 import os
 import sys
@@ -53,8 +57,34 @@ def config_a():
                         bc=marker.numpy(), g=g.numpy())
 
 
+def delaunay_tets_n4():
+    """An unstructured tetrahedral mesh of the unit cube: the 5 x 5 x 5 lattice (h = 1/4), every
+    coordinate that does not lie on a boundary plane moved by 0.25 h U(-1, 1), Delaunay-triangulated;
+    the vertex order of every cell as qhull returns it (both orientation signs occur). The archive is
+    written with fixed member dates, so a rerun reproduces the file byte for byte."""
+    import zipfile
+
+    from scipy.spatial import Delaunay
+
+    n = 4
+    h = 1.0 / n
+    ax = np.linspace(0.0, 1.0, n + 1)
+    X, Y, Z = np.meshgrid(ax, ax, ax, indexing="ij")  # vertex k + 5 (j + 5 i) at (i, j, k) h
+    x = np.stack([X.reshape(-1), Y.reshape(-1), Z.reshape(-1)], 1)
+    rng = np.random.default_rng(1)
+    jitter = 0.25 * h * rng.uniform(-1.0, 1.0, size=x.shape)
+    inside = (x > 1e-12) & (x < 1.0 - 1e-12)  # per coordinate: a face vertex slides within its face
+    x = np.where(inside, x + jitter, x)
+    cells = Delaunay(x).simplices.astype(np.int32)
+    with zipfile.ZipFile(os.path.join(HERE, "delaunay_tets_n4.npz"), "w", zipfile.ZIP_STORED) as z:
+        for name, a in (("x", np.ascontiguousarray(x, dtype=np.float64)), ("cells", np.ascontiguousarray(cells))):
+            with z.open(zipfile.ZipInfo(name + ".npy", date_time=(1980, 1, 1, 0, 0, 0)), "w") as f:
+                np.lib.format.write_array(f, a, allow_pickle=False)
+
+
 if __name__ == "__main__":
     O.build()
-    square()
-    config_a()
+    makers = dict(square=square, config_a=config_a, delaunay_tets_n4=delaunay_tets_n4)
+    for name in sys.argv[1:] or list(makers):  # (all, or the ones named on the command line)
+        makers[name]()
     print("golden fixtures written to", HERE)

@@ -18,6 +18,7 @@ import numpy as np
 import pytest
 import torch
 
+from irregular_meshes import fan
 from rowparity import RTOL
 
 pytestmark = pytest.mark.gpu
@@ -265,21 +266,11 @@ def test_permuted_node_numbering(oracle, dev, name):
     _check_block_diag(op, S, f"permuted {name}")
 
 
-def _fan(dev, ntri=300):
-    """ntri triangles around vertex 0: more cells at one node than a chunk's 256-cell tile holds."""
-    from femasm import mesh
-
-    t = torch.arange(ntri, dtype=torch.float64) * (2 * np.pi / ntri)
-    x = torch.cat([torch.zeros(1, 2, dtype=torch.float64), torch.stack([torch.cos(t), torch.sin(t)], 1)])
-    i = torch.arange(ntri)
-    cells = torch.stack([torch.zeros_like(i), 1 + i, 1 + (i + 1) % ntri], 1).to(torch.int32)
-    return mesh.Mesh(mesh.CellType.triangle, x.to(dev), cells.to(dev))
-
-
 def test_fan_mesh_falls_back_to_generic(oracle, dev):
+    """300 triangles around vertex 0: more cells at one node than a chunk's 256-cell tile holds."""
     from femasm import _lib, fem
 
-    m = _fan(dev)
+    m = fan(300, dev)
     V = fem.functionspace(m, ("Lagrange", 1, (2,)))
     a = _form(oracle, V, "lin", 1.0)
     ring = torch.nonzero(m.x[:, 0] > 0.5, as_tuple=False).reshape(-1)

@@ -42,6 +42,45 @@ def test_bsr_mult_and_block_diag(oracle, dev):
         np.testing.assert_array_equal(D[r], Sd[3 * r:3 * r + 3, 3 * r:3 * r + 3])
 
 
+def test_bsr_mult_and_block_diag_bs1(dev):
+    """Block size 1 (scalar CSR through k_bsr_mult<1>): a random pattern with an empty row and a row with
+    no diagonal entry, y pre-filled with NaN (every row must be written, the empty one with 0). Per row
+    |y - Ax|_i <= 1e-14 (|A||x|)_i: a row of n <= 12 products summed in order carries at most
+    n * 2^-53 ~ 1.4e-15 of (|A||x|)_i, in the kernel and in scipy alike."""
+    from femasm.la import MatrixCSR
+
+    n = 301  # two workgroups of 256 rows
+    rng = np.random.default_rng(4)
+    rows = []
+    for r in range(n):
+        k = 0 if r == 7 else int(rng.integers(1, 13))
+        c = np.sort(rng.choice(n, size=k, replace=False))
+        if r == 11:
+            c = c[c != r]  # no diagonal entry
+        elif k and r % 3 == 0 and r not in c:
+            c = np.sort(np.append(c[:-1], r))
+        rows.append(c.astype(np.int32))
+    assert len(rows[7]) == 0 and len(rows[11]) > 0 and 11 not in rows[11]
+    indptr = np.concatenate([[0], np.cumsum([len(c) for c in rows])]).astype(np.int64)
+    indices = np.concatenate(rows).astype(np.int32)
+    data = rng.uniform(-1.0, 1.0, size=(len(indices), 1, 1))
+    xh = rng.uniform(-2.0, 2.0, size=n)
+    A = MatrixCSR(torch.tensor(indptr, device=dev), torch.tensor(indices, device=dev), 1, torch.tensor(data, device=dev))
+    y = torch.full((n,), float("nan"), dtype=torch.float64, device=dev)
+    out = A.mult(torch.tensor(xh, device=dev), y)
+    assert out.data_ptr() == y.data_ptr()
+    S = sps.csr_matrix((data.reshape(-1), indices, indptr), shape=(n, n))
+    ref, scale = S @ xh, abs(S) @ np.abs(xh)
+    yh = _np(y)
+    assert np.isfinite(yh).all() and yh[7] == 0.0
+    err = np.abs(yh - ref)
+    print(f"bs=1 mult: worst row |y - Ax| / (|A||x|) = {(err[scale > 0] / scale[scale > 0]).max():.3e}")
+    assert (err <= 1e-14 * scale).all()
+    D = _np(A.block_diagonal()).reshape(-1)
+    np.testing.assert_array_equal(D, S.diagonal())
+    assert D[7] == 0.0 and D[11] == 0.0
+
+
 def _oracle_newton(oracle, kind, ct, p, V, m, lam, mu, u0, marker, gv, f=None, d=None, rtol=1e-7, atol=5e-8,
                    max_it=10):
     """dolfinx NewtonSolver iteration on the CPU with the oracle's residual / tangent."""
