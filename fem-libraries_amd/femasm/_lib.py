@@ -21,6 +21,7 @@ FA_GATHER, FA_SCATTER, FA_ZERO_FIRST, FA_DETERMINISTIC, FA_CHECK_ERRORS = 0x0, 0
 FA_KEEP_COEF = 0x10
 FA_PLAN_AFFINE, FA_PLAN_DETERMINISTIC, FA_PLAN_ORDER_SEARCH, FA_PLAN_NEO = 0x1, 0x2, 0x4, 0x8
 FA_EVAL_GRAD, FA_EVAL_STRAIN, FA_EVAL_STRESS, FA_EVAL_ENERGY = 0x1, 0x2, 0x4, 0x8
+FA_LOAD_NONE, FA_LOAD_CONSTANT, FA_LOAD_FACET, FA_LOAD_NODAL = 0, 1, 2, 3
 
 
 class FemasmError(RuntimeError):
@@ -124,6 +125,26 @@ class fa_edge_transfer(ctypes.Structure):
     ]
 
 
+class fa_facet_load(ctypes.Structure):
+    _fields_ = [
+        ("nfacets", ctypes.c_int64),
+        ("nloaded", ctypes.c_int64),
+        ("nvalues", ctypes.c_int64),
+        ("nk", ctypes.c_int32),
+        ("qdeg", ctypes.c_int32),
+        ("facet_cell", ctypes.c_void_p),
+        ("facet_local", ctypes.c_void_p),
+        ("facet_value", ctypes.c_void_p),
+        ("nodes", ctypes.c_void_p),
+        ("node_ptr", ctypes.c_void_p),
+        ("entries", ctypes.c_void_p),
+        ("traction_mode", ctypes.c_int32),
+        ("pressure_mode", ctypes.c_int32),
+        ("traction", ctypes.c_void_p),
+        ("pressure", ctypes.c_void_p),
+    ]
+
+
 # exported symbols with their signatures; tests check every one against include/femasm.h
 P = ctypes.c_void_p
 I32, I64, D = ctypes.c_int32, ctypes.c_int64, ctypes.c_double
@@ -175,6 +196,7 @@ SIGNATURES = {
     "fa_edge_midpoints": (ctypes.c_int, [I64, I32, P, P, P, P]),
     "fa_prolong_edges": (ctypes.c_int, [P, P, P, P, I32, P, P]),
     "fa_restrict_edges": (ctypes.c_int, [P, P, P, P, P, P]),
+    "fa_facet_load_apply": (ctypes.c_int, [P, P, D, P, P]),
     "fa_hbm_probe": (ctypes.c_int, [I32, P, P, I64, P]),
 }
 

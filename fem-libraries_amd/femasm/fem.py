@@ -459,12 +459,15 @@ class LinearElasticity:
     """J of the reference form with damage d = 0:
     inner(sigma(du), eps(v)) dx, sigma = lmbda tr(eps) I + 2 mu eps, mu = E/(2(1+nu)),
     lmbda = E nu/((1+nu)(1-2nu))  (FEniCSx/mechanic2d/asym_ufl.py:22-34, :78-83).
-    E: DG0 Function / per-cell tensor / float; nu: Constant / float. Alternatively lam & mu per cell."""
+    E: DG0 Function / per-cell tensor / float; nu: Constant / float. Alternatively lam & mu per cell.
+    loads: ``SurfaceLoad`` objects on V; ``assemble_vector`` subtracts each after the cell term (dead loads:
+    the matrix and the Jacobian action do not see them)."""
     kind = _lib.FA_LINEAR_ELASTICITY
 
     def __init__(self, V: FunctionSpace, E=None, nu=0.3, lam=None, mu=None, quadrature_degree: int | None = None,
-                 u=None, f=None):
+                 u=None, f=None, loads=None):
         self.V = V
+        self.loads = _check_loads(V, loads)
         nc = V.mesh.num_cells
         dev = V.mesh.device
         self.nu = float(nu)
@@ -488,11 +491,11 @@ class AsymDamage(LinearElasticity):
     kind = _lib.FA_ASYM_DAMAGE
 
     def __init__(self, V: FunctionSpace, E=None, nu=0.3, u=None, d=None, lam=None, mu=None, f=None,
-                 tangent: str = "hand"):
+                 tangent: str = "hand", loads=None):
         """tangent: "hand" (the reference's default build: eigen-decomposition tangent and stress,
         :207-329, :766-881) or "ad" (its USE_AD build: forward-over-forward AD of the damage
         potential, :100-204, :752-763)."""
-        super().__init__(V, E=E, nu=nu, lam=lam, mu=mu, quadrature_degree=1, u=u, f=f)
+        super().__init__(V, E=E, nu=nu, lam=lam, mu=mu, quadrature_degree=1, u=u, f=f, loads=loads)
         self.d = None if d is None else (d.x if isinstance(d, Function) else d)
         if tangent not in ("hand", "ad"):
             raise ValueError(f"tangent must be 'hand' or 'ad', not {tangent!r}")
@@ -508,10 +511,24 @@ class NeoHookean(LinearElasticity):
     MFEM AD, MFEM/mechanic2d/autodiff/admfem.hpp:672-700). u: the state (required)."""
     kind = _lib.FA_NEO_HOOKEAN
 
-    def __init__(self, V: FunctionSpace, E=None, nu=0.3, u=None, lam=None, mu=None, quadrature_degree=None, f=None):
+    def __init__(self, V: FunctionSpace, E=None, nu=0.3, u=None, lam=None, mu=None, quadrature_degree=None, f=None,
+                 loads=None):
         if u is None:
             raise ValueError("NeoHookean needs the state u")
-        super().__init__(V, E=E, nu=nu, lam=lam, mu=mu, quadrature_degree=quadrature_degree, u=u, f=f)
+        super().__init__(V, E=E, nu=nu, lam=lam, mu=mu, quadrature_degree=quadrature_degree, u=u, f=f, loads=loads)
+
+
+def _check_loads(V: FunctionSpace, loads):
+    """The loads list of a form on V (None when there is none)."""
+    if not loads:
+        return None
+    loads = [loads] if isinstance(loads, SurfaceLoad) else list(loads)
+    for ld in loads:
+        if not isinstance(ld, SurfaceLoad):
+            raise TypeError(f"loads holds a {type(ld).__name__}, not a SurfaceLoad")
+        if ld.V is not V and (ld.V.mesh is not V.mesh or ld.V.degree != V.degree or ld.V.num_dofs != V.num_dofs):
+            raise ValueError("a SurfaceLoad of another function space")
+    return loads
 
 
 def _cellwise(v, nc, dev):
@@ -1161,8 +1178,11 @@ def tabulate_cells(a, c0: int = 0, ncells: int | None = None) -> torch.Tensor:
 
 def assemble_vector(L, b: torch.Tensor | None = None) -> torch.Tensor:
     """Residual of the form's constitutive law: b += int sigma(u):eps(v) dxx - int f.v dx
+    - sum over the form's loads of int (t - p n).v ds
     (dolfinx.fem.assemble_vector of the reference F, FEniCSx/mechanic2d/asym_elasto_damage_model.cc:825;
-    MFEM damIntegrator::AssembleElementVector :559-637). u, f are the form's `u` / `f` (None = 0)."""
+    MFEM damIntegrator::AssembleElementVector :559-637). u, f are the form's `u` / `f` (None = 0); each
+    ``SurfaceLoad`` of the form's `loads` is subtracted after the cell term (``assemble_surface_load``
+    with alpha = -1). Without loads the launches are the cell term's alone."""
     V = L.V
     if b is None:
         b = torch.zeros(V.num_dofs, dtype=torch.float64, device=V.mesh.device)
@@ -1172,6 +1192,8 @@ def assemble_vector(L, b: torch.Tensor | None = None) -> torch.Tensor:
     adj = V._fa_adjacency()
     _lib.check(Lb.fa_assemble_vector(ctypes.byref(fm), ctypes.byref(ff), ctypes.byref(adj), b.data_ptr(),
                                      _lib.stream_handle(V.mesh.device)), "fa_assemble_vector")
+    for ld in getattr(L, "loads", None) or ():
+        assemble_surface_load(ld, b, alpha=-1.0)
     return b
 
 
@@ -1211,8 +1233,356 @@ def set_bc(b: torch.Tensor, bcs: list, x0=None, alpha: float = 1.0, scale=None):
     return b
 
 
+# ---------------------------------------------------------------------------------- exterior-facet loads
+def _space_basis(ct, p: int, X: np.ndarray) -> np.ndarray:
+    """Degree-p Lagrange basis (basix node order) at reference points X [n, tdim] -> [n, nn]."""
+    ct = CellType(ct)
+    if is_simplex(ct):
+        lam = np.concatenate([1.0 - X.sum(1, keepdims=True), X], axis=1)
+        if p == 1:
+            return lam
+        if p != 2:
+            raise NotImplementedError("simplex degree > 2")
+        return np.concatenate([lam * (2.0 * lam - 1.0)] + [4.0 * lam[:, [i]] * lam[:, [j]] for i, j in _EDGES[ct]], axis=1)
+    r = line_points(p)
+    l1 = []  # per direction, the 1-D Lagrange polynomials at the points [n, p + 1]
+    for d in range(X.shape[1]):
+        cols = []
+        for i in range(p + 1):
+            v = np.ones(X.shape[0])
+            for k in range(p + 1):
+                if k != i:
+                    v = v * (X[:, d] - r[k]) / (r[i] - r[k])
+            cols.append(v)
+        l1.append(np.stack(cols, 1))
+    L = node_lattice(ct, p)
+    out = np.ones((X.shape[0], L.shape[0]))
+    for d in range(X.shape[1]):
+        out = out * l1[d][:, L[:, d]]
+    return out
+
+
+def _geometry_gradients(ct, X: np.ndarray) -> np.ndarray:
+    """Reference gradients of the P1 / Q1 geometry basis at X [n, tdim] -> [n, nverts, tdim]."""
+    ct = CellType(ct)
+    n, td = X.shape
+    if is_simplex(ct):
+        g = np.concatenate([-np.ones((1, td)), np.eye(td)], 0)
+        return np.broadcast_to(g, (n, td + 1, td)).copy()
+    out = np.empty((n, len(_REF_VERTS[ct]), td))
+    for v, bits in enumerate(_REF_VERTS[ct]):
+        f = [X[:, d] if bits[d] else 1.0 - X[:, d] for d in range(td)]
+        for k in range(td):
+            gk = np.full(n, 1.0 if bits[k] else -1.0)
+            for d in range(td):
+                if d != k:
+                    gk = gk * f[d]
+            out[:, v, k] = gk
+    return out
+
+
+def _gauss_01(n: int):
+    x, w = np.polynomial.legendre.leggauss(n)
+    return 0.5 * (x + 1.0), 0.5 * w
+
+
+def _facet_rule(ct, qdeg: int):
+    """(points [nq, tdim - 1], weights [nq]) on the reference facet of a cell type, the library's rules:
+    Gauss on [0, 1]; on a triangle the 1- and 3-point rules up to degree 2, a collapsed Gauss product above;
+    a Gauss product with (qdeg + 2) // 2 points per direction on a quadrilateral."""
+    ct = CellType(ct)
+    if ct in (CellType.triangle, CellType.quadrilateral):
+        x, w = _gauss_01((qdeg + 2) // 2)
+        return x.reshape(-1, 1), w
+    if ct == CellType.hexahedron:
+        x, w = _gauss_01((qdeg + 2) // 2)
+        return np.array([[a, b] for a in x for b in x]), np.array([u * v for u in w for v in w])
+    if qdeg == 1:
+        return np.array([[1.0 / 3.0, 1.0 / 3.0]]), np.array([0.5])
+    if qdeg == 2:
+        a, b = 1.0 / 6.0, 2.0 / 3.0
+        return np.array([[a, a], [a, b], [b, a]]), np.full(3, 1.0 / 6.0)
+    x, w = _gauss_01((qdeg + 2) // 2 + 1)
+    return (np.array([[a * (1.0 - b), b] for a in x for b in x]),
+            np.array([u * v * (1.0 - b) for u in w for v, b in zip(w, x)]))
+
+
+_FACET_TABLES = {}
+
+
+def _facet_tables(ct, p: int, qdeg: int) -> dict:
+    """Facet tables of an element, per local facet (mesh.sub_entities(ct, tdim - 1)): the facet rule mapped
+    into the cell through the facet's reference vertices, X = V0 + xi (V1 - V0) + eta (V2 - V0); wq [nq],
+    phi [nl, nq, nn], gdphi [nl, nq, nv, td], nref [nl, td] = the outward N_ref dS_ref of that
+    parametrisation, closure [nl, nk] = _closure_nodes of each local facet."""
+    ct = CellType(ct)
+    key = (ct, p, qdeg)
+    if key in _FACET_TABLES:
+        return _FACET_TABLES[key]
+    from .mesh import sub_entities
+
+    RV = np.array(_REF_VERTS[ct], dtype=np.float64)
+    td = RV.shape[1]
+    pts, wq = _facet_rule(ct, qdeg)
+    phi, gd, nref, closure = [], [], [], []
+    for S in sub_entities(ct, td - 1):
+        V0, A = RV[S[0]], RV[S[1]] - RV[S[0]]
+        X = V0 + pts[:, [0]] * A
+        if td == 3:
+            B = RV[S[2]] - RV[S[0]]
+            X = X + pts[:, [1]] * B
+            N = np.cross(A, B)
+        else:
+            N = np.array([A[1], -A[0]])
+        if N @ (X.mean(0) - RV.mean(0)) < 0.0:
+            N = -N
+        phi.append(_space_basis(ct, p, X))
+        gd.append(_geometry_gradients(ct, X))
+        nref.append(N)
+        closure.append(_closure_nodes(ct, p, S))
+    T = dict(wq=wq, phi=np.stack(phi), gdphi=np.stack(gd), nref=np.stack(nref), closure=np.array(closure, dtype=np.int64))
+    _FACET_TABLES[key] = T
+    return T
+
+
+class SurfaceLoad:
+    """A dead load on exterior facets of V's mesh: ``int (t - p n).v ds`` on the reference configuration,
+    the reference's ``dot(t*n, delta_u)*ds(0)`` term (FEniCSx/mechanic2d/asym_ufl.py:81; its scalar t is -p).
+
+    facets: ids of ``mesh.entities(m, tdim - 1)`` (what ``mesh.locate_entities_boundary``,
+    ``mesh.exterior_facets`` and ``io.MeshTags.find`` return), each exterior and given once.
+    traction ``t``, a force per reference area: one gdim-vector; a ``[len(facets), gdim]`` tensor of
+    per-facet values in the order of ``facets``; or nodal values, a ``Function`` on V or a ``[num_dofs]``
+    tensor, interpolated with the cell basis at the facet points.
+    pressure ``p``, along the reference OUTWARD unit normal n (the traction is -p n): a scalar; a
+    ``[len(facets)]`` tensor; or nodal values, a ``Function`` on a scalar space with V's nodes or a
+    ``[num_nodes]`` tensor. A plain tensor of ``len(facets)`` entries is per-facet: where that count equals
+    ``num_nodes``, nodal values have to come as a Function.
+    Both may be given and add. Tensors (and Functions) are read at every assembly, like a form's ``E``:
+    changing them in place costs nothing. quadrature_degree: None = 2 * degree, the rule of the f.v dx term.
+
+    The plan is built here, once, in torch: the facets sorted by id (slots), each slot's cell and local facet
+    (``mesh.sub_entities`` numbering) from ``entities()``'s cell -> facet table, and a node-parallel
+    adjacency over the loaded nodes only: ``nodes`` (ascending), a CSR ``node_ptr`` and entries
+    ``slot * nk + k`` with k indexing ``_closure_nodes(ct, p, S_local_facet)``, a node's entries in
+    ascending slot order. The sum order is therefore fixed: results are bit-identical run to run and under
+    any permutation of ``facets`` (per-facet values following their facets).
+
+    Out of scope: follower (deformation-dependent) pressure and its unsymmetric tangent, interior-facet and
+    Robin terms, and ``parallel.SlabProblem`` (a slab's cut planes are exterior facets of the slab mesh)."""
+
+    def __init__(self, V: FunctionSpace, facets, traction=None, pressure=None, quadrature_degree: int | None = None):
+        from . import mesh as fmesh
+
+        m = V.mesh
+        if V.family in ("DG", "Discontinuous Lagrange") or V.bs != m.gdim:
+            raise ValueError("a SurfaceLoad needs a vector Lagrange space (bs = gdim)")
+        if traction is None and pressure is None:
+            raise ValueError("a SurfaceLoad needs a traction, a pressure or both")
+        if quadrature_degree is not None and not 1 <= int(quadrature_degree) <= 12:
+            raise ValueError(f"quadrature_degree {quadrature_degree} outside 1 .. 12")
+        self.V = V
+        self.qdeg = -1 if quadrature_degree is None else int(quadrature_degree)
+        dev = m.device
+        f = torch.as_tensor(facets, device=dev)
+        if f.dim() != 1 or f.dtype.is_floating_point or f.dtype == torch.bool:
+            raise ValueError("facets must be a 1-D tensor of facet ids")
+        f = f.to(torch.int64)
+        _, cf = fmesh.entities(m, m.tdim - 1)
+        nfac = int(cf.max()) + 1 if cf.numel() else 0
+        if f.numel() and (int(f.min()) < 0 or int(f.max()) >= nfac):
+            raise ValueError(f"facet ids outside [0, {nfac})")
+        order = torch.argsort(f, stable=True)
+        fs = f[order]
+        if fs.numel() > 1 and bool((fs[1:] == fs[:-1]).any()):
+            raise ValueError("a facet is given twice")
+        flat = cf.reshape(-1)
+        cnt = torch.bincount(flat, minlength=nfac)
+        if bool((cnt[fs] != 1).any()):
+            bad = fs[cnt[fs] != 1]
+            raise ValueError(f"{bad.numel()} of the facets are not exterior (first: facet {int(bad[0])})")
+        self.facets = f
+        nf, nl = int(f.numel()), int(cf.shape[1])
+        # slot -> (cell, local facet): an exterior facet has one position in the cell -> facet table
+        pos = torch.zeros(nfac, dtype=torch.int64, device=dev)
+        pos[flat] = torch.arange(flat.numel(), device=dev)
+        hit = pos[fs]
+        cell, lf = hit // nl, hit % nl
+        CL = torch.tensor([_closure_nodes(m.cell_type, V.degree, S) for S in fmesh.sub_entities(m.cell_type, m.tdim - 1)],
+                          dtype=torch.int64, device=dev)  # [nl, nk]
+        nk = int(CL.shape[1])
+        if nf * nk > 2 ** 31 - 1:
+            raise ValueError(f"{nf} facets of {nk} nodes: more entries than int32 holds")
+        fnodes = torch.gather(V.dofmap.to(torch.int64)[cell], 1, CL[lf])  # [nf, nk]
+        # entries slot * nk + k by node; the stable sort keeps a node's entries in ascending slot order
+        flatn = fnodes.reshape(-1)
+        perm = torch.argsort(flatn, stable=True)
+        nodes, counts = torch.unique_consecutive(flatn[perm], return_counts=True)
+        ptr = torch.zeros(nodes.numel() + 1, dtype=torch.int64, device=dev)
+        ptr[1:] = torch.cumsum(counts, 0)
+        self.nk = nk
+        self.facet_cell = cell.to(torch.int32).contiguous()
+        self.facet_local = lf.to(torch.int32).contiguous()
+        self.facet_value = order.to(torch.int32).contiguous()  # slot -> row of the per-facet values as given
+        self.nodes = nodes.to(torch.int32).contiguous()
+        self.node_ptr = ptr
+        self.entries = perm.to(torch.int32).contiguous()
+        self._traction = self._value_source(traction, "traction", m.gdim)
+        self._pressure = self._value_source(pressure, "pressure", 1)
+
+    def _value_source(self, v, name: str, width: int):
+        """(mode, holder) of a value argument: the holder is a device tensor, or the Function whose ``x`` is
+        read at every assembly."""
+        V = self.V
+        if v is None:
+            return (_lib.FA_LOAD_NONE, None)
+        if isinstance(v, Function):
+            W = v.function_space
+            if W.mesh is not V.mesh or W.bs != width or W.num_nodes != V.num_nodes or W.degree != V.degree or \
+                    W.family in ("DG", "Discontinuous Lagrange"):
+                raise ValueError(f"the {name} Function must live on V's nodes with {width} value(s) per node")
+            return (_lib.FA_LOAD_NODAL, v)
+        if isinstance(v, Constant):
+            v = v.value
+        t = torch.as_tensor(v, dtype=torch.float64, device=V.mesh.device).contiguous()
+        nf = int(self.facets.numel())
+        if width == 1:
+            if t.numel() == 1 and t.dim() <= 1:
+                return (_lib.FA_LOAD_CONSTANT, t.reshape(1))
+            if t.dim() == 1 and t.numel() == nf:
+                return (_lib.FA_LOAD_FACET, t)
+            if t.dim() == 1 and t.numel() == V.num_nodes:
+                return (_lib.FA_LOAD_NODAL, t)
+            raise ValueError(f"pressure of shape {tuple(t.shape)}: a scalar, [{nf}] per facet or [{V.num_nodes}] per node")
+        if t.dim() == 1 and t.numel() == width:
+            return (_lib.FA_LOAD_CONSTANT, t)
+        if t.dim() == 2 and tuple(t.shape) == (nf, width):
+            return (_lib.FA_LOAD_FACET, t)
+        if t.dim() == 1 and t.numel() == V.num_dofs:
+            return (_lib.FA_LOAD_NODAL, t)
+        raise ValueError(f"traction of shape {tuple(t.shape)}: [{width}], [{nf}, {width}] per facet or [{V.num_dofs}] per dof")
+
+    def _values(self, src, name: str, nodal_size: int):
+        mode, h = src
+        if h is None:
+            return mode, None
+        t = h.x if isinstance(h, Function) else h
+        if isinstance(h, Function) and (t.dtype != torch.float64 or t.numel() != nodal_size or not t.is_contiguous()
+                                        or t.device != self.V.mesh.device):
+            raise ValueError(f"the {name} Function's values changed shape, type or device")
+        return mode, t
+
+    def values(self):
+        """((traction mode, tensor | None), (pressure mode, tensor | None)) as this assembly reads them."""
+        V = self.V
+        return self._values(self._traction, "traction", V.num_dofs), self._values(self._pressure, "pressure", V.num_nodes)
+
+    def _fa_facet_load(self, tv, pv) -> _lib.fa_facet_load:
+        s = _lib.fa_facet_load()
+        s.nfacets, s.nloaded, s.nvalues = int(self.facets.numel()), int(self.nodes.numel()), int(self.facets.numel())
+        s.nk, s.qdeg = self.nk, self.qdeg
+        s.facet_cell, s.facet_local, s.facet_value = (self.facet_cell.data_ptr(), self.facet_local.data_ptr(),
+                                                      self.facet_value.data_ptr())
+        s.nodes, s.node_ptr, s.entries = self.nodes.data_ptr(), self.node_ptr.data_ptr(), self.entries.data_ptr()
+        s.traction_mode, s.traction = tv[0], _lib.ptr(tv[1])
+        s.pressure_mode, s.pressure = pv[0], _lib.ptr(pv[1])
+        return s
+
+
+def _surface_load_host(load: SurfaceLoad, alpha: float, b: torch.Tensor) -> torch.Tensor:
+    """Plain-torch definition of ``assemble_surface_load`` (any device; what a mesh on the CPU runs). Per slot
+    and facet point: J = sum_v x_v (x) gdphi_v, n dS = sign(det J) cof(J) N_ref dS_ref (the cofactor's columns
+    are cross products of J's columns: no inverse), dS = |n dS|; then each node's entries summed in the
+    plan's order."""
+    V = load.V
+    m = V.mesh
+    gd, dev = m.gdim, m.device
+    qd = 2 * V.degree if load.qdeg < 0 else load.qdeg
+    Tn = _facet_tables(m.cell_type, V.degree, qd)
+    T = {k: torch.as_tensor(v, device=dev) for k, v in Tn.items()}
+    cell, lf = load.facet_cell.to(torch.int64), load.facet_local.to(torch.int64)
+    nf, nk = int(cell.numel()), load.nk
+    if nf == 0:
+        return b
+    (tmode, tval), (pmode, pval) = load.values()
+    xv = m.x[m.cells.to(torch.int64)[cell]]  # [nf, nv, gd]
+    J = torch.einsum("fvi,fqvk->fqik", xv, T["gdphi"][lf])  # [nf, nq, gd, gd]
+    N = T["nref"][lf][:, None, :]  # [nf, 1, gd]
+    if gd == 2:
+        det = J[..., 0, 0] * J[..., 1, 1] - J[..., 0, 1] * J[..., 1, 0]
+        nds = torch.stack([J[..., 1, 1] * N[..., 0] - J[..., 1, 0] * N[..., 1],
+                           J[..., 0, 0] * N[..., 1] - J[..., 0, 1] * N[..., 0]], -1)
+    else:
+        j0, j1, j2 = J[..., 0], J[..., 1], J[..., 2]
+        c0, c1, c2 = torch.cross(j1, j2, dim=-1), torch.cross(j2, j0, dim=-1), torch.cross(j0, j1, dim=-1)
+        det = (j0 * c0).sum(-1)
+        nds = c0 * N[..., 0:1] + c1 * N[..., 1:2] + c2 * N[..., 2:3]
+    sign = torch.where(det < 0.0, -torch.ones_like(det), torch.ones_like(det))
+    nds = sign[..., None] * nds  # [nf, nq, gd]
+    dS = torch.sqrt((nds * nds).sum(-1))  # [nf, nq]
+    phi = T["phi"][lf]  # [nf, nq, nn]
+    nq = phi.shape[1]
+    rows = load.facet_value.to(torch.int64)
+    dm = V.dofmap.to(torch.int64)[cell]  # [nf, nn]
+    g = torch.zeros((nf, nq, gd), dtype=torch.float64, device=dev)
+    if tmode != _lib.FA_LOAD_NONE:
+        if tmode == _lib.FA_LOAD_CONSTANT:
+            tq = tval.reshape(1, 1, gd)
+        elif tmode == _lib.FA_LOAD_FACET:
+            tq = tval[rows][:, None, :]
+        else:
+            tq = torch.einsum("fqb,fbi->fqi", phi, tval.reshape(-1, gd)[dm])
+        g = g + tq * dS[..., None]
+    if pmode != _lib.FA_LOAD_NONE:
+        if pmode == _lib.FA_LOAD_CONSTANT:
+            pq = pval.reshape(1, 1)
+        elif pmode == _lib.FA_LOAD_FACET:
+            pq = pval[rows][:, None]
+        else:
+            pq = torch.einsum("fqb,fb->fq", phi, pval[dm])
+        g = g - pq[..., None] * nds
+    aloc = T["closure"][lf]  # [nf, nk]
+    pha = torch.gather(phi, 2, aloc[:, None, :].expand(nf, nq, nk))  # [nf, nq, nk]
+    contrib = torch.einsum("q,fqk,fqi->fki", T["wq"], pha, g).reshape(nf * nk, gd)
+    # a node's entries in the plan's order: pass j adds every node's j-th entry
+    ptr, ent = load.node_ptr, load.entries.to(torch.int64)
+    counts = ptr[1:] - ptr[:-1]
+    r = torch.zeros((int(load.nodes.numel()), gd), dtype=torch.float64, device=dev)
+    for j in range(int(counts.max())):
+        sel = counts > j
+        r[sel] += contrib[ent[ptr[:-1][sel] + j]]
+    bv = b.view(-1, gd)
+    nodes = load.nodes.to(torch.int64)
+    bv[nodes] = bv[nodes] + float(alpha) * r
+    return b
+
+
+def assemble_surface_load(load: SurfaceLoad, b: torch.Tensor | None = None, alpha: float = 1.0) -> torch.Tensor:
+    """b += alpha * int (t - p n).v ds over the load's facets; returns b (zeros when None). The linear form
+    of a linear problem A u = b (dolfinx.fem.assemble_vector of ``dot(t, v)*ds - p*dot(n, v)*ds``); a form
+    with ``loads`` subtracts it in ``assemble_vector``. A mesh on the GPU runs k_facet_load
+    (fa_facet_load_apply: one thread per loaded node, no atomics, bit-identical run to run), one on the CPU
+    the same definition in torch (``_surface_load_host``)."""
+    if not isinstance(load, SurfaceLoad):
+        raise TypeError("expected a SurfaceLoad")
+    V = load.V
+    dev = V.mesh.device
+    if b is None:
+        b = torch.zeros(V.num_dofs, dtype=torch.float64, device=dev)
+    elif b.dtype != torch.float64 or b.dim() != 1 or b.numel() != V.num_dofs or not b.is_contiguous() or b.device != dev:
+        raise ValueError(f"b must be a contiguous float64 vector of {V.num_dofs} entries on {dev}")
+    if dev.type != "cuda":
+        return _surface_load_host(load, alpha, b)
+    tv, pv = load.values()
+    fm = V._fa_mesh()
+    fl = load._fa_facet_load(tv, pv)
+    _lib.check(_lib.load().fa_facet_load_apply(ctypes.byref(fm), ctypes.byref(fl), float(alpha), b.data_ptr(),
+                                              _lib.stream_handle(dev)), "fa_facet_load_apply")
+    return b
+
+
 # ---------------------------------------------------------------------------------- expressions
-QUANTITIES = ("grad", "strain", "stress", "energy")
+QUANTITIES =("grad", "strain", "stress", "energy")
 
 
 def interpolation_points(ct) -> np.ndarray:

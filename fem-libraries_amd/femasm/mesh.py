@@ -406,3 +406,115 @@ def refine(m: Mesh) -> Mesh:
     _lib.check(L.fa_refine_cells(int(m.cell_type), nc, nv, mc.data_ptr(), ce32.data_ptr(), mx.data_ptr(),
                                  _lib.ptr(mt), cells.data_ptr(), _lib.ptr(tags), sh), "fa_refine_cells")
     return Mesh(m.cell_type, x, cells, tags, None, m)
+
+
+# ---------------------------------------------------------------------------------- facet tags
+def _find_rows(ent: torch.Tensor, rows: torch.Tensor, what: str) -> torch.Tensor:
+    """Ids in ``ent`` (the sorted unique vertex tuples of ``entities``) of the sorted vertex tuples ``rows``:
+    the union's unique rows are ``ent`` again exactly when every row is one of its entities."""
+    if rows.shape[0] == 0:
+        return torch.zeros(0, dtype=torch.int64, device=ent.device)
+    uniq, inv = _unique_rows(torch.cat([ent, rows], 0))
+    if uniq.shape[0] != ent.shape[0]:
+        raise ValueError(f"{what}: not an entity of the mesh")
+    return inv[ent.shape[0]:]
+
+
+_GMSH_SUB = {0: {15: 1}, 1: {1: 2}, 2: {2: 3, 3: 4}}  # dim -> Gmsh element type -> vertices
+
+
+def read_gmsh_tags(path: str, mesh: Mesh, dim: int):
+    """The lower-dimensional physical groups of a Gmsh 2.2 ASCII file as an ``io.MeshTags`` of dimension
+    ``dim`` < tdim on ``mesh = read_gmsh(path)``: lines (dim 1), triangles and quadrilaterals (dim 2) or
+    points (dim 0), each mapped to its id in ``entities(mesh, dim)`` (vertex indices for dim 0) and tagged
+    with its physical group — the facet markers gmshio hands dolfinx next to the cell tags, which
+    ``read_gmsh`` drops. Indices sorted (int32), values int32, on the mesh's device."""
+    from .io import MeshTags
+
+    if not 0 <= dim < mesh.tdim or dim not in _GMSH_SUB:
+        raise ValueError(f"tags of dimension 0 .. {mesh.tdim - 1} of a {mesh.cell_type.name} mesh, not {dim}")
+    with open(path) as fh:
+        lines = [ln.strip() for ln in fh]
+    i = lines.index("$Nodes")
+    nnod = int(lines[i + 1])
+    coords = {}
+    for ln in lines[i + 2:i + 2 + nnod]:
+        p = ln.split()
+        coords[int(p[0])] = [float(v) for v in p[1:4]]
+    i = lines.index("$Elements")
+    nel = int(lines[i + 1])
+    top = {2: CellType.triangle, 3: CellType.quadrilateral, 4: CellType.tetrahedron, 5: CellType.hexahedron}
+    cell_et = {v: k for k, v in top.items()}[mesh.cell_type]
+    used, sub = set(), []
+    for ln in lines[i + 2:i + 2 + nel]:
+        p = [int(v) for v in ln.split()]
+        et, ntag = p[1], p[2]
+        if et == cell_et:
+            used.update(p[3 + ntag:])
+        elif et in _GMSH_SUB[dim]:
+            sub.append((p[3], p[3 + ntag:]))
+    # read_gmsh's vertex numbering: the cells' nodes in ascending file id
+    used = sorted(used)
+    remap = {old: new for new, old in enumerate(used)}
+    x = torch.tensor([coords[n][:mesh.gdim] for n in used], dtype=torch.float64)
+    if x.shape[0] != mesh.num_vertices or not torch.equal(x, mesh.x.cpu()):
+        raise ValueError(f"{path}: its cells' vertices are not the mesh's (pass the mesh read_gmsh built from it)")
+    dev = mesh.device
+    if not sub:
+        z = torch.zeros(0, dtype=torch.int32, device=dev)
+        return MeshTags(dim, z, z.clone())
+    if any(n not in remap for _, ns in sub for n in ns):
+        raise ValueError(f"{path}: a tagged entity of dimension {dim} has a node no cell uses")
+    width = {len(ns) for _, ns in sub}
+    ent, _ = entities(mesh, dim)
+    if len(width) != 1 or width.pop() != ent.shape[1]:
+        raise ValueError(f"{path}: tagged entities of dimension {dim} do not match the mesh's cell type")
+    rows = torch.sort(torch.tensor([[remap[n] for n in ns] for _, ns in sub], dtype=torch.int64, device=dev), dim=1).values
+    ids = _find_rows(ent, rows, f"{path}: a tagged entity of dimension {dim}")
+    vals = torch.tensor([t for t, _ in sub], dtype=torch.int32, device=dev)
+    order = torch.argsort(ids, stable=True)
+    ids, vals = ids[order], vals[order]
+    if ids.numel() > 1 and bool((ids[1:] == ids[:-1]).any()):
+        raise ValueError(f"{path}: an entity of dimension {dim} is tagged twice")
+    return MeshTags(dim, ids.to(torch.int32), vals)
+
+
+def transfer_facet_tags(tags, fine: Mesh):
+    """Facet tags of ``fine.parent`` carried to ``fine = refine(fine.parent)``, as an ``io.MeshTags`` of the
+    same dimension: with ``refine``'s numbering (vertex ``nv + e`` is the midpoint of parent edge ``e``) a
+    tagged edge (a, b) becomes its two child edges (a, m_ab), (m_ab, b), a tagged triangle (a, b, c) its
+    four child triangles (a, m_ab, m_ac), (b, m_ab, m_bc), (c, m_ac, m_bc), (m_ab, m_ac, m_bc), each with the
+    parent's value. ``refine`` inherits cell tags only; this keeps boundary markers through the
+    refine-then-multigrid workflow. Torch only, on the meshes' device."""
+    from .io import MeshTags
+
+    coarse = fine.parent
+    if coarse is None:
+        raise ValueError("transfer_facet_tags needs a refined mesh (fine.parent is None)")
+    if tags.dim != coarse.tdim - 1:
+        raise ValueError(f"facet tags have dimension {coarse.tdim - 1}, not {tags.dim}")
+    dev = fine.device
+    nv = coarse.num_vertices
+    ev, _ = entities(coarse, 1)
+    idx = tags.indices.to(dev).to(torch.int64)
+    vals = tags.values.to(dev).to(torch.int32)
+    fent, _ = entities(coarse, tags.dim)
+    if idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= fent.shape[0]):
+        raise ValueError(f"tagged facet ids outside [0, {fent.shape[0]})")
+    if tags.dim == 1:
+        a, b = ev[idx, 0], ev[idx, 1]
+        mid = nv + idx
+        kids = torch.stack([torch.stack([a, mid], 1), torch.stack([b, mid], 1)], 1)  # [n, 2, 2]
+    else:
+        a, b, c = fent[idx, 0], fent[idx, 1], fent[idx, 2]  # ascending: the pairs below are sorted too
+        mab = nv + _find_rows(ev, torch.stack([a, b], 1), "a tagged triangle's edge")
+        mac = nv + _find_rows(ev, torch.stack([a, c], 1), "a tagged triangle's edge")
+        mbc = nv + _find_rows(ev, torch.stack([b, c], 1), "a tagged triangle's edge")
+        kids = torch.stack([torch.stack([a, mab, mac], 1), torch.stack([b, mab, mbc], 1),
+                            torch.stack([c, mac, mbc], 1), torch.stack([mab, mac, mbc], 1)], 1)  # [n, 4, 3]
+    nchild, k = kids.shape[1], kids.shape[2]
+    rows = torch.sort(kids.reshape(-1, k), dim=1).values
+    ids = _find_rows(entities(fine, tags.dim)[0], rows, "a child facet")
+    cvals = vals.repeat_interleave(nchild)
+    order = torch.argsort(ids, stable=True)
+    return MeshTags(tags.dim, ids[order].to(torch.int32), cvals[order].contiguous(), getattr(tags, "name", "mesh_tags"))

@@ -415,6 +415,10 @@ class SlabProblem:
         if self.mode != "exchange":
             raise NotImplementedError("assemble_residual: exchange mode")
         V, a = self.V, self.a
+        if getattr(a, "loads", None):
+            # a slab's cut planes are exterior facets of the slab mesh, and a facet on the true boundary is
+            # assembled by every rank that holds it: surface loads are single-GPU (fem.SurfaceLoad)
+            raise NotImplementedError("SlabProblem does not take surface loads (fem.SurfaceLoad is single-GPU)")
         if b is None:
             b = torch.zeros(V.num_dofs, dtype=torch.float64, device=V.mesh.device)
         else:

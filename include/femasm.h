@@ -28,6 +28,8 @@
  *                        damIntegrator::AssembleElementVector (:559-637).
  *   fa_apply_lifting,    dolfinx::fem::apply_lifting / set_bc as called from setF
  *   fa_set_bc            (FEniCSx/mechanic2d/asym_elasto_damage_model.cc:827, :836).
+ *   fa_facet_load_apply  the exterior_facet integrals of that assemble_vector: `- dot(t*n, delta_u)*ds(0)`
+ *                        (FEniCSx/mechanic2d/asym_ufl.py:81; USE_SURF, asym_elasto_damage_model.cc:589-608).
  */
 #ifndef FEMASM_H
 #define FEMASM_H
@@ -530,6 +532,65 @@ int fa_prolong_edges(const fa_edge_transfer* t, const double* xc, const int8_t* 
                      const int8_t* bc_f /* or NULL */, int32_t add, double* xf, void* stream);
 int fa_restrict_edges(const fa_edge_transfer* t, const double* rf, const int8_t* bc_f /* or NULL */,
                       const int8_t* bc_c /* or NULL */, double* rc, void* stream);
+
+/* ---- exterior-facet loads: surface tractions and pressure (femasm_facet.hip, fa_version() >= 106) ----
+ * The facet term of the reference's residual, `- dot(t*n, delta_u)*ds(0)` (FEniCSx/mechanic2d/asym_ufl.py:81,
+ * with the exterior_facet subdomain data of its "5.2 Neumann setting", asym_elasto_damage_model.cc:589-608,
+ * switched off there for a dolfinx 0.8.0 bug in pack_coefficient_entity): what dolfinx::fem::assemble_vector
+ * adds for the exterior_facet integrals of a linear form.
+ *
+ *   b[a, i] += alpha * sum over the loaded facets F of node a of  int_F (t_i - p n_i) phi_a dS
+ *
+ * on the REFERENCE configuration (dead loads: nothing depends on the state u, so there is no tangent).
+ * t is a force per reference area, p a pressure along the reference OUTWARD unit normal n: the traction of
+ * a pressure is -p n (the reference's scalar t in t*n is -p). At a facet point X (cell reference
+ * coordinates) J = sum_v x_v (x) grad psi_v(X) with the P1 / Q1 geometry basis and, by Nanson's formula,
+ *   n dS = sign(det J) cof(J) N_ref dS_ref     (cof(J) = det(J) J^-T, formed without the inverse),
+ * outward for either cell orientation; dS = |n dS|. J is taken at every point: bilinear hexahedron faces
+ * and non-affine quadrilaterals are integrated as they are. Facet rule: Gauss on [0, 1] (2-D), the
+ * library's triangle / quadrilateral rule (3-D) of degree qdeg, mapped into the cell through the local
+ * facet's reference vertices X = V0 + xi (V1 - V0) + eta (V2 - V0).
+ *
+ * The plan (host-built once per facet set, all DEVICE arrays): the loaded facets as slots 0 .. nfacets-1
+ * (femasm sorts them by facet id), each with its one cell and its local facet index in basix's
+ * sub-entity numbering (triangle edges (1,2),(0,2),(0,1); quadrilateral edges (0,1),(0,2),(1,3),(2,3);
+ * tetrahedron face i opposite vertex i; hexahedron faces (0,1,2,3),(0,1,4,5),(0,2,4,6),(1,3,5,7),
+ * (2,3,6,7),(4,5,6,7)); the loaded nodes as a compact list with a CSR over entries slot * nk + k, where
+ * k counts the nodes of the local facet's closure in ascending local node order (nk per facet: p + 1 on
+ * an edge, (p+1)(p+2)/2 on a triangle, (p+1)^2 on a quadrilateral face). A node's entries are summed in
+ * the order stored (femasm: ascending slot), one thread per loaded node, one write per dof, no atomics:
+ * bit-identical run to run. Entries, cells, local facets, value rows and nodes out of range are skipped
+ * on the device, never dereferenced. */
+#define FA_LOAD_NONE 0     /* the value is absent (its pointer is ignored) */
+#define FA_LOAD_CONSTANT 1 /* one value for every facet: traction [gdim], pressure [1] */
+#define FA_LOAD_FACET 2    /* one value per facet: traction [nvalues][gdim], pressure [nvalues]; slot s reads row
+                              facet_value[s] */
+#define FA_LOAD_NODAL 3    /* nodal values in the mesh's space, interpolated with the cell basis at the facet
+                              points: traction [nnodes][gdim], pressure [nnodes] */
+typedef struct {
+  int64_t nfacets;             /* loaded facets (slots) */
+  int64_t nloaded;             /* loaded nodes */
+  int64_t nvalues;             /* rows of the FA_LOAD_FACET value arrays */
+  int32_t nk;                  /* nodes in a facet's closure (checked against the element) */
+  int32_t qdeg;                /* facet quadrature degree; < 0 = 2 * degree (the rule of the f.v dx term) */
+  const int32_t* facet_cell;   /* [nfacets] the facet's cell */
+  const int32_t* facet_local;  /* [nfacets] its local facet index in that cell */
+  const int32_t* facet_value;  /* [nfacets] its row of the per-facet value arrays */
+  const int32_t* nodes;        /* [nloaded] loaded nodes, each once */
+  const int64_t* node_ptr;     /* [nloaded + 1] CSR over entries */
+  const int32_t* entries;      /* [node_ptr[nloaded]] slot * nk + k */
+  int32_t traction_mode;       /* FA_LOAD_* */
+  int32_t pressure_mode;       /* FA_LOAD_* */
+  const double* traction;      /* DEVICE values, read at every call */
+  const double* pressure;
+} fa_facet_load;
+
+/* b += alpha * (the integral above). Asynchronous; no allocation and no synchronisation after the first
+ * call per (element, qdeg), which caches the facet tables on the device like the cell tables. Every
+ * supported cell type and degree (P1 / P2 simplices, Q1 .. Q3). Replaces the exterior_facet part of
+ * dolfinx::fem::assemble_vector(b, L) for L = dot(t, v)*ds(k) - p*dot(n, v)*ds(k). Out of scope: follower
+ * (deformation-dependent) pressure and its unsymmetric tangent, interior-facet and Robin terms. */
+int fa_facet_load_apply(const fa_mesh* mesh, const fa_facet_load* load, double alpha, double* b, void* stream);
 
 /* Measurement helper (not part of the reference interface): a 16-B-per-lane grid-stride stream
  * over n doubles (n even, 16-B aligned buffers) for the measured HBM peak beside the 8 TB/s spec
