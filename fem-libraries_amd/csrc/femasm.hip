@@ -4691,7 +4691,11 @@ extern "C" int fa_plan_order(const fa_mesh* mesh, const fa_adjacency* adj, const
 }
 
 // Tensor cells: is every cell affine (x_v = x_0 + J xi_v at all vertices, J from vertices 1, 2, 4)?
-// Sets *nonaffine when one is not (tolerance: 1e-12 of the cell's size).
+// Sets *nonaffine when one is not. Tolerance: dev <= 1e-13 h, dev the largest component by which a vertex
+// misses the parallelepiped of the three edges, h the cell's largest coordinate extent. The affine route
+// assembles that parallelepiped, which costs up to 3.0 dev / h per matrix row against the trilinear cell
+// (measured: tests/test_invariance_host.py, worst on Q3 hexahedra), so 1e-13 keeps it at 3e-13, inside
+// half of the 1e-12 per-row bar; the 1e-12 it was admitted 2.6e-12 (profiles/invariance/near_threshold_tol_1e-12.txt).
 template <int GD>
 __global__ void k_check_affine(MeshView M, int* nonaffine) {
   constexpr int NV = 1 << GD;
@@ -4714,7 +4718,7 @@ __global__ void k_check_affine(MeshView M, int* nonaffine) {
         dev = fmax(dev, fabs(x[v][i] - pred));
         h = fmax(h, fabs(x[v][i] - x[0][i]));
       }
-    if (dev > 1e-12 * h) atomicOr(nonaffine, 1);
+    if (dev > 1e-13 * h) atomicOr(nonaffine, 1);
   }
 }
 

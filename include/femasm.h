@@ -130,7 +130,9 @@ typedef struct {
 /* fa_plan.cell_flags */
 #define FA_PLAN_AFFINE 0x1   /* every cell of a tensor mesh is a parallelogram / parallelepiped: its
                                 hexahedra assemble through the affine row gather (no element-matrix
-                                store); otherwise through the MFMA element kernel + block gather */
+                                store); otherwise through the MFMA element kernel + block gather.
+                                Every vertex within 1e-13 of the cell's size of the parallelepiped of
+                                the edges at vertex 0 (the affine route's error is up to 3x that) */
 #define FA_PLAN_DETERMINISTIC 0x2 /* set by the caller: assemblies with this plan (fa_assemble_matrix and
                                      fa_gather_rows) are deterministic, as with FA_DETERMINISTIC */
 #define FA_PLAN_ORDER_SEARCH 0x4  /* set by the caller before fa_plan_order: also run the alternating-path
