@@ -22,6 +22,7 @@ FA_KEEP_COEF = 0x10
 FA_PLAN_AFFINE, FA_PLAN_DETERMINISTIC, FA_PLAN_ORDER_SEARCH, FA_PLAN_NEO = 0x1, 0x2, 0x4, 0x8
 FA_EVAL_GRAD, FA_EVAL_STRAIN, FA_EVAL_STRESS, FA_EVAL_ENERGY = 0x1, 0x2, 0x4, 0x8
 FA_LOAD_NONE, FA_LOAD_CONSTANT, FA_LOAD_FACET, FA_LOAD_NODAL = 0, 1, 2, 3
+FA_FUNC_MEASURE, FA_FUNC_STRAIN_ENERGY, FA_FUNC_L2, FA_FUNC_H1 = 0, 1, 2, 3
 
 
 class FemasmError(RuntimeError):
@@ -197,6 +198,9 @@ SIGNATURES = {
     "fa_prolong_edges": (ctypes.c_int, [P, P, P, P, I32, P, P]),
     "fa_restrict_edges": (ctypes.c_int, [P, P, P, P, P, P]),
     "fa_facet_load_apply": (ctypes.c_int, [P, P, D, P, P]),
+    "fa_quadrature": (ctypes.c_int, [I32, I32, P, P, P]),
+    "fa_functional_work_bytes": (ctypes.c_int, [P, P]),
+    "fa_assemble_scalar": (ctypes.c_int, [P, P, I32, P, P, I32, P, P, I64, P, P]),
     "fa_hbm_probe": (ctypes.c_int, [I32, P, P, I64, P]),
 }
 

@@ -1691,3 +1691,364 @@ class Expression:
         if mesh is not None and mesh is not self.form.V.mesh:
             raise ValueError("the Expression's form lives on another mesh")
         return evaluate(self.form, (self.quantity,), X=self.X, cells=cells)[self.quantity]
+
+
+# ---------------------------------------------------------------------------------- scalar functionals
+def quadrature(cell_type, qdeg: int):
+    """(points [nq, tdim], weights [nq]) of the library's rule of degree qdeg on the reference cell, as numpy
+    arrays (fa_quadrature: host only; the rule every kernel integrates with, not a copy of it)."""
+    L = _lib.load()
+    ct = int(CellType(cell_type))
+    nq = ctypes.c_int32(0)
+    _lib.check(L.fa_quadrature(ct, int(qdeg), ctypes.byref(nq), None, None), "fa_quadrature")
+    td = len(_REF_VERTS[CellType(cell_type)][0])
+    pts, wts = np.empty((nq.value, td)), np.empty(nq.value)
+    _lib.check(L.fa_quadrature(ct, int(qdeg), ctypes.byref(nq), pts.ctypes.data, wts.ctypes.data), "fa_quadrature")
+    return pts, wts
+
+
+def quadrature_points(V: FunctionSpace, qdeg: int) -> torch.Tensor:
+    """Physical coordinates [ncells, nq, gdim] of the degree-qdeg rule's points in every cell (the geometry
+    map applied to ``quadrature(...)[0]``): ``g = exact(xq)`` for ``L2Norm2``."""
+    m = V.mesh
+    X, _ = quadrature(m.cell_type, qdeg)
+    Psi = torch.tensor(_geometry_basis(m.cell_type, X), dtype=torch.float64, device=m.device)  # [nq, nv]
+    return torch.einsum("qv,cvd->cqd", Psi, m.x[m.cells.to(torch.int64)])
+
+
+def _space_basis_gradients(ct, p: int, X: np.ndarray) -> np.ndarray:
+    """Reference gradients of the degree-p Lagrange basis (basix node order) at X [n, tdim] -> [n, nn, tdim]."""
+    ct = CellType(ct)
+    n, td = X.shape
+    if is_simplex(ct):
+        lam = np.concatenate([1.0 - X.sum(1, keepdims=True), X], axis=1)  # [n, nv]
+        gl = np.concatenate([-np.ones((1, td)), np.eye(td)], 0)  # [nv, td]
+        if p == 1:
+            return np.broadcast_to(gl, (n, td + 1, td)).copy()
+        if p != 2:
+            raise NotImplementedError("simplex degree > 2")
+        out = [(4.0 * lam[:, :, None] - 1.0) * gl[None]]
+        for i, j in _EDGES[ct]:
+            out.append(4.0 * (lam[:, [i], None] * gl[None, [j]] + lam[:, [j], None] * gl[None, [i]]))
+        return np.concatenate(out, axis=1)
+    r = line_points(p)
+    v1, d1 = [], []  # per direction, the 1-D Lagrange polynomials and derivatives at the points [n, p + 1]
+    for d in range(td):
+        vc, dc = [], []
+        for i in range(p + 1):
+            v = np.ones(n)
+            dv = np.zeros(n)
+            for k in range(p + 1):
+                if k != i:
+                    t = (X[:, d] - r[k]) / (r[i] - r[k])
+                    dv = dv * t + v / (r[i] - r[k])
+                    v = v * t
+            vc.append(v)
+            dc.append(dv)
+        v1.append(np.stack(vc, 1))
+        d1.append(np.stack(dc, 1))
+    L = node_lattice(ct, p)
+    out = np.ones((n, L.shape[0], td))
+    for k in range(td):
+        for d in range(td):
+            out[:, :, k] *= (d1 if d == k else v1)[d][:, L[:, d]]
+    return out
+
+
+def _field(w):
+    return w.x if isinstance(w, Function) else w
+
+
+class Measure:
+    """int 1 dx over V's mesh (any rule is exact on affine cells)."""
+    kind = _lib.FA_FUNC_MEASURE
+
+    def __init__(self, V: FunctionSpace, qdeg: int | None = None):
+        self.V, self.qdeg = V, qdeg
+
+
+class StrainEnergy:
+    """int psi(grad u) dx of the form's law at its state ``form.u``, on the form's own rule: the potential
+    whose gradient is ``assemble_vector``'s sigma term. Linear: lam/2 tr(eps)^2 + mu eps:eps; NeoHookean:
+    mu/2 (I_C - 3) - mu ln J + lam/2 (ln J)^2 (non-finite when a cell is inverted); AsymDamage: the
+    reference's damage potential with the mean nodal damage of the cell."""
+    kind = _lib.FA_FUNC_STRAIN_ENERGY
+
+    def __init__(self, form):
+        if not isinstance(form, LinearElasticity):
+            raise TypeError("expected a femasm form descriptor (LinearElasticity, AsymDamage, NeoHookean)")
+        self.form, self.V, self.qdeg = form, form.V, None
+
+
+class L2Norm2:
+    """int |w - g|^2 dx: w a Function or nodal tensor on V, g [ncells, nq, bs] values at
+    ``quadrature_points(V, qdeg)`` (None: zero); qdeg None = 2 * degree."""
+    kind = _lib.FA_FUNC_L2
+
+    def __init__(self, w, g=None, qdeg: int | None = None, V: FunctionSpace | None = None):
+        self.V = w.function_space if isinstance(w, Function) else V
+        if self.V is None:
+            raise ValueError("a nodal tensor needs its space: L2Norm2(w, V=V)")
+        self.w, self.g, self.qdeg = w, g, qdeg
+
+
+class H1Semi2(L2Norm2):
+    """int |grad w - G|^2 dx: G [ncells, nq, bs, gdim] values at the rule's points (None: zero)."""
+    kind = _lib.FA_FUNC_H1
+
+    def __init__(self, w, G=None, qdeg: int | None = None, V: FunctionSpace | None = None):
+        super().__init__(w, G, qdeg, V)
+
+
+class TotalEnergy:
+    """Pi(u) = StrainEnergy(form) - dot(u, b_ext) with b_ext = -assemble_vector(the form without its state):
+    the body force on the degree-2p rule and every ``SurfaceLoad``, from the residual's own kernels, so that
+    grad Pi(u) is exactly ``assemble_vector(form)``. b_ext is held by the object; ``refresh()`` rebuilds it
+    after the force or a load's values changed."""
+
+    def __init__(self, form):
+        self.strain = StrainEnergy(form)
+        self.form, self.V = form, form.V
+        self.b_ext = None
+        self.refresh()
+
+    def refresh(self):
+        import copy
+
+        ext = copy.copy(self.form)
+        # no state: the sigma term vanishes whatever the law, so the copy is a plain linear form (the
+        # library refuses a neo-Hookean form without u)
+        ext.u, ext.d, ext.kind = None, None, _lib.FA_LINEAR_ELASTICITY
+        V = self.V
+        if V.mesh.device.type == "cuda":
+            self.b_ext = assemble_vector(ext).neg_()
+        else:
+            b = _body_force_host(ext)
+            for ld in getattr(ext, "loads", None) or ():
+                assemble_surface_load(ld, b, alpha=1.0)
+            self.b_ext = b
+        return self
+
+
+def _func_qdeg(M) -> int:
+    """The rule's degree as the library resolves it (fa_assemble_scalar)."""
+    V = M.V
+    ct, p = V.mesh.cell_type, V.degree
+    est = 2 * (p - 1) if is_simplex(ct) else 2 * p
+    if M.kind == _lib.FA_FUNC_STRAIN_ENERGY:
+        if M.form.kind in (_lib.FA_ASYM_DAMAGE, _lib.FA_ASYM_DAMAGE_AD):
+            return 1
+        q = M.form.qdeg
+        return est if q < 0 else q
+    if M.qdeg is not None and M.qdeg >= 0:
+        return int(M.qdeg)
+    return max(1, est) if M.kind == _lib.FA_FUNC_MEASURE else 2 * p
+
+
+def _host_geometry(V: FunctionSpace, qdeg: int):
+    """(wd [nc, nq], gphys [nc, nq, nn, gd], |dphi| |J^-1| majorant of gphys, phi [nq, nn]) on any device."""
+    m = V.mesh
+    dev = m.device
+    X, wq = quadrature(m.cell_type, qdeg)
+    phi = torch.as_tensor(_space_basis(m.cell_type, V.degree, X), device=dev)
+    dphi = torch.as_tensor(_space_basis_gradients(m.cell_type, V.degree, X), device=dev)
+    gd = torch.as_tensor(_geometry_gradients(m.cell_type, X), device=dev)
+    xv = m.x[m.cells.to(torch.int64)]  # [nc, nv, gd]
+    J = torch.einsum("cvi,qvk->cqik", xv, gd)
+    if J.shape[0] == 0:
+        z = torch.zeros((0, len(wq)), dtype=torch.float64, device=dev)
+        g0 = torch.zeros((0, len(wq), phi.shape[1], m.gdim), dtype=torch.float64, device=dev)
+        return z, g0, g0, phi
+    Ji = torch.linalg.inv(J)
+    wd = torch.as_tensor(wq, device=dev)[None, :] * torch.linalg.det(J).abs()
+    gphys = torch.einsum("qbk,cqkd->cqbd", dphi, Ji)
+    gabs = torch.einsum("qbk,cqkd->cqbd", dphi.abs(), Ji.abs())
+    return wd, gphys, gabs, phi
+
+
+def _body_force_host(form) -> torch.Tensor:
+    """int f.v dx on the degree-2p rule in torch (the load term of k_vector with the sign of a right-hand side)."""
+    V = form.V
+    dev = V.mesh.device
+    b = torch.zeros(V.num_dofs, dtype=torch.float64, device=dev)
+    if form.f is None:
+        return b
+    bs = V.bs
+    wd, _, _, phi = _host_geometry(V, 2 * V.degree)
+    dm = V.dofmap.to(torch.int64)
+    fq = torch.einsum("qb,cbi->cqi", phi, form.f.view(-1, bs)[dm])
+    contrib = torch.einsum("cq,qa,cqi->cai", wd, phi, fq)
+    b.view(-1, bs).index_add_(0, dm.reshape(-1), contrib.reshape(-1, bs))
+    return b
+
+
+def _perm_abs(Fa: torch.Tensor) -> torch.Tensor:
+    """The determinant's expansion with every product taken in absolute value (Fa >= 0), [..., gd, gd]."""
+    if Fa.shape[-1] == 2:
+        return Fa[..., 0, 0] * Fa[..., 1, 1] + Fa[..., 0, 1] * Fa[..., 1, 0]
+    a = Fa
+    return (a[..., 0, 0] * (a[..., 1, 1] * a[..., 2, 2] + a[..., 1, 2] * a[..., 2, 1])
+            + a[..., 0, 1] * (a[..., 1, 0] * a[..., 2, 2] + a[..., 1, 2] * a[..., 2, 0])
+            + a[..., 0, 2] * (a[..., 1, 0] * a[..., 2, 1] + a[..., 1, 1] * a[..., 2, 0]))
+
+
+def _det(F: torch.Tensor) -> torch.Tensor:
+    if F.shape[-1] == 2:
+        return F[..., 0, 0] * F[..., 1, 1] - F[..., 0, 1] * F[..., 1, 0]
+    return (F[..., 0, 0] * (F[..., 1, 1] * F[..., 2, 2] - F[..., 1, 2] * F[..., 2, 1])
+            - F[..., 0, 1] * (F[..., 1, 0] * F[..., 2, 2] - F[..., 1, 2] * F[..., 2, 0])
+            + F[..., 0, 2] * (F[..., 1, 0] * F[..., 2, 1] - F[..., 1, 1] * F[..., 2, 0]))
+
+
+def assemble_scalar_host(M):
+    """The functionals' definitions in differentiable torch, on the mesh's device (what a mesh on the CPU
+    runs): (cell integrals [nc], magnitudes [nc]). A cell's magnitude is its integral evaluated with every
+    product replaced by its absolute value and every difference by a sum (for ln J and the principal strains,
+    whose arguments cancel, the first-order bound of their error): rounding moves the cell integral by a
+    few units of 1.1e-16 times it, which is what the device parity bars are stated in. ``TotalEnergy`` has
+    no per-cell split: use its ``strain`` part."""
+    if isinstance(M, TotalEnergy):
+        raise ValueError("TotalEnergy has no per-cell split: pass M.strain")
+    V = M.V
+    bs = V.bs
+    if V.family in ("DG", "Discontinuous Lagrange") or bs != V.mesh.gdim:
+        raise ValueError("functionals live on a vector Lagrange space (bs = gdim)")
+    wd, gp, ga, phi = _host_geometry(V, _func_qdeg(M))
+    dm = V.dofmap.to(torch.int64)
+    if M.kind == _lib.FA_FUNC_MEASURE:
+        v = wd.sum(1)
+        return v, v.detach().abs()
+    if M.kind in (_lib.FA_FUNC_L2, _lib.FA_FUNC_H1):
+        wc = _field(M.w).view(-1, bs)[dm]  # [nc, nn, bs]
+        if M.kind == _lib.FA_FUNC_L2:
+            val = torch.einsum("qb,cbi->cqi", phi, wc)
+            mag = torch.einsum("qb,cbi->cqi", phi.abs(), wc.abs())
+        else:
+            val = torch.einsum("cbi,cqbk->cqik", wc, gp)
+            mag = torch.einsum("cbi,cqbk->cqik", wc.abs(), ga)
+        if M.g is not None:
+            g = M.g.reshape(val.shape)
+            val, mag = val - g, mag + g.abs()
+        s = (val * val).reshape(val.shape[0], val.shape[1], -1).sum(2)
+        sm = (mag * mag).reshape(val.shape[0], val.shape[1], -1).sum(2)
+        return (wd * s).sum(1), (wd * sm).sum(1).detach()
+    form = M.form
+    if form.u is None:
+        raise ValueError("the strain energy needs the form's state u")
+    if form.E is not None:
+        mu = form.E / (2.0 * (1.0 + form.nu))
+        lam = form.E * form.nu / ((1.0 + form.nu) * (1.0 - 2.0 * form.nu))
+    else:
+        lam, mu = form.lam, form.mu
+    lam, mu = lam[:, None], mu[:, None]
+    uc = form.u.view(-1, bs)[dm]
+    gu = torch.einsum("cbi,cqbk->cqik", uc, gp)
+    gua = torch.einsum("cbi,cqbk->cqik", uc.detach().abs(), ga)
+    eye = torch.eye(bs, dtype=torch.float64, device=gu.device)
+
+    def lin(g):
+        tr = g.diagonal(dim1=-2, dim2=-1).sum(-1)
+        eps = 0.5 * (g + g.transpose(-1, -2))
+        return tr, (eps * eps).sum((-1, -2))
+
+    if form.kind == _lib.FA_NEO_HOOKEAN:
+        F, Fa = gu + eye, gua + eye
+        Jd = _det(F)
+        lnJ = torch.log(Jd)
+        psi = 0.5 * mu * ((F * F).sum((-1, -2)) - bs) - mu * lnJ + 0.5 * lam * lnJ * lnJ
+        with torch.no_grad():
+            ln = lnJ.abs()
+            pm = (0.5 * mu.abs() * ((Fa * Fa).sum((-1, -2)) + bs) + mu.abs() * ln + 0.5 * lam.abs() * ln * ln
+                  + (mu.abs() + lam.abs() * ln) * _perm_abs(Fa) / Jd.abs())
+    else:
+        tr, ee = lin(gu)
+        psi = 0.5 * lam * tr * tr + mu * ee
+        tra, eea = lin(gua)
+        pm = 0.5 * lam.abs() * tra * tra + mu.abs() * eea
+        if form.kind in (_lib.FA_ASYM_DAMAGE, _lib.FA_ASYM_DAMAGE_AD) and form.d is not None:
+            d = form.d[dm].sum(1, keepdim=True) * (1.0 / 3.0)  # [nc, 1]: the mean nodal damage, unclamped
+            e11, e22, e12 = gu[..., 0, 0], gu[..., 1, 1], 0.5 * (gu[..., 0, 1] + gu[..., 1, 0])
+            I1, I2 = e11 + e22, e12 * e12 - e11 * e22
+            with torch.no_grad():
+                nz = (I1.abs() > 1e-12) | (I2.abs() > 1e-12)
+            delta = torch.where(nz, I1 * I1 + 4.0 * I2, torch.ones_like(I1))
+            r = torch.sqrt(delta)
+            ev1, ev2 = 0.5 * (I1 + r), 0.5 * (I1 - r)
+            with torch.no_grad():
+                a1, a2 = (ev1 >= 0).to(gu.dtype), (ev2 >= 0).to(gu.dtype)
+                al = ((ev1 + ev2) >= 0).to(gu.dtype)
+            p_dam = 0.5 * (1.0 - al * d) * lam * (I1 * I1) + mu * ((1.0 - a1 * d) * ev1 * ev1 + (1.0 - a2 * d) * ev2 * ev2)
+            p_null = (1.0 - d) * (0.5 * lam * (I1 * I1) + mu * (e11 * e11 + e22 * e22 + 2.0 * e12 * e12))
+            psi = torch.where(d > 0, torch.where(nz, p_dam, p_null), psi)
+            with torch.no_grad():
+                I1a = gua[..., 0, 0] + gua[..., 1, 1]
+                e12a = 0.5 * (gua[..., 0, 1] + gua[..., 1, 0])
+                da = I1a * I1a + 4.0 * (e12a * e12a + gua[..., 0, 0] * gua[..., 1, 1])
+                eva = 0.5 * (I1a + da / r)  # r's error is bounded by eps * da / (2 r), and r <= da / r
+                pd = 0.5 * lam.abs() * I1a * I1a + 2.0 * mu.abs() * eva * eva
+                pm = torch.where(d > 0, torch.where(nz, pd, pm), pm)
+    return (wd * psi).sum(1), (wd * pm).sum(1).detach()
+
+
+def _functional_work(V: FunctionSpace, fm) -> torch.Tensor:
+    """The reduction's workspace, cached on V (the library allocates nothing per call)."""
+    nb = ctypes.c_int64(0)
+    _lib.check(_lib.load().fa_functional_work_bytes(ctypes.byref(fm), ctypes.byref(nb)), "fa_functional_work_bytes")
+    wk = V.__dict__.get("_functional_work")
+    if wk is None or wk.numel() < nb.value or wk.device != V.mesh.device:
+        wk = torch.empty(nb.value, dtype=torch.uint8, device=V.mesh.device)
+        V.__dict__["_functional_work"] = wk
+    return wk
+
+
+def assemble_scalar(M, cellwise: bool = False, out: torch.Tensor | None = None) -> torch.Tensor:
+    """dolfinx.fem.assemble_scalar for a functional descriptor (``Measure``, ``StrainEnergy``, ``L2Norm2``,
+    ``H1Semi2``, ``TotalEnergy``): a 0-d float64 tensor on the mesh's device (nothing is synchronised: the
+    caller's ``float()`` does), or with ``cellwise=True`` the [ncells] cell integrals. A mesh on the GPU runs
+    k_functional_cells (every cell once, one lane per cell) and k_functional_reduce (fixed-order sums, no
+    atomics: bit-identical run to run); a mesh on the CPU runs ``assemble_scalar_host``, differentiable with
+    respect to a state that requires grad. out: optional preallocated result (GPU meshes; every entry is
+    written)."""
+    if isinstance(M, TotalEnergy):
+        if cellwise:
+            raise ValueError("TotalEnergy has no per-cell split: pass M.strain")
+        return assemble_scalar(M.strain) - torch.dot(M.form.u, M.b_ext)
+    if not isinstance(M, (Measure, StrainEnergy, L2Norm2)):
+        raise TypeError("expected a functional descriptor (Measure, StrainEnergy, L2Norm2, H1Semi2, TotalEnergy)")
+    V = M.V
+    dev = V.mesh.device
+    if dev.type != "cuda":
+        cells, _ = assemble_scalar_host(M)
+        return cells if cellwise else cells.sum()
+    nc = V.mesh.num_cells
+    if V.family in ("DG", "Discontinuous Lagrange") or V.bs != V.mesh.gdim:
+        raise ValueError("functionals live on a vector Lagrange space (bs = gdim)")
+    w = g = None
+    ff = None
+    if M.kind == _lib.FA_FUNC_STRAIN_ENERGY:
+        if M.form.u is None:
+            raise ValueError("the strain energy needs the form's state u")
+        ff = _fa_form(M.form)
+    elif M.kind != _lib.FA_FUNC_MEASURE:
+        w = _field(M.w)
+        if w.dtype != torch.float64 or w.numel() != V.num_dofs or not w.is_contiguous() or w.device != dev:
+            raise ValueError(f"w must be a contiguous float64 vector of {V.num_dofs} entries on {dev}")
+        if M.g is not None:
+            nq = len(quadrature(V.mesh.cell_type, _func_qdeg(M))[1])
+            per = V.bs * (V.mesh.gdim if M.kind == _lib.FA_FUNC_H1 else 1)
+            g = M.g
+            if g.dtype != torch.float64 or g.numel() != nc * nq * per or not g.is_contiguous() or g.device != dev:
+                raise ValueError(f"g must be a contiguous float64 tensor of {nc} x {nq} x {per} values on {dev}")
+    fm = V._fa_mesh()
+    wk = _functional_work(V, fm)
+    if out is None:
+        out = torch.empty(nc if cellwise else (), dtype=torch.float64, device=dev)
+    elif out.dtype != torch.float64 or out.device != dev or not out.is_contiguous() or \
+            out.shape != ((nc,) if cellwise else ()):
+        raise ValueError(f"out must be a contiguous float64 tensor of shape {(nc,) if cellwise else ()} on {dev}")
+    qd = -1 if getattr(M, "qdeg", None) is None else int(M.qdeg)
+    _lib.check(_lib.load().fa_assemble_scalar(
+        ctypes.byref(fm), None if ff is None else ctypes.byref(ff), int(M.kind), _lib.ptr(w), _lib.ptr(g), qd,
+        out.data_ptr() if cellwise else None, wk.data_ptr(), wk.numel(), None if cellwise else out.data_ptr(),
+        _lib.stream_handle(dev)), "fa_assemble_scalar")
+    return out

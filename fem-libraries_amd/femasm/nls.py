@@ -22,6 +22,12 @@ C++: asym_elasto_damage_model.cc:705-714, 820-890) — with every operator on th
   geometric multigrid V-cycle on the structured meshes (femasm.mg), whose iteration count does not
   grow like 1/h.
 
+* ``NewtonSolver.line_search = "energy"`` globalises the iteration by backtracking on the potential
+  Pi(u) = ``fem.TotalEnergy(F)`` (strain energy minus the work of the body force and the dead loads; its
+  gradient is the assembled residual): steps 1, 1/2, .. 2^-10 until Pi is finite and meets the Armijo
+  condition. dolfinx's NewtonSolver has no line search (PETSc SNES users pick ``-snes_linesearch_type bt``);
+  the default ``None`` is dolfinx's plain update.
+
 Single GPU (the assembly's multi-GPU path is ``femasm.parallel``; a distributed Krylov solve is
 not part of this module).
 """
@@ -75,6 +81,35 @@ class NonlinearProblem:
             self._A = fem.JacobianOperator(self.a, bcs=self.bcs, diagonal=1.0) if self.matrix_free \
                 else fem.create_matrix(self.a)
         return self._A
+
+    # ---- the potential of F, for NewtonSolver.line_search = "energy"
+    def total_energy(self) -> fem.TotalEnergy:
+        """Pi = fem.TotalEnergy(F) (built on first use: one assemble_vector for b_ext)."""
+        if getattr(self, "_Pi", None) is None:
+            self._Pi = fem.TotalEnergy(self.L)
+        return self._Pi
+
+    def energy(self, x: torch.Tensor) -> float:
+        """Pi(x): the strain energy of F's law minus the work of its body force and loads; grad Pi = the
+        assembled residual. x is the problem's state or a trial vector (then the state is restored)."""
+        Pi = self.total_energy()
+        ux = self.u.x
+        if x.data_ptr() == ux.data_ptr():
+            return float(fem.assemble_scalar(Pi))
+        keep = ux.clone()
+        ux.copy_(x)
+        try:
+            return float(fem.assemble_scalar(Pi))
+        finally:
+            ux.copy_(keep)
+
+    def prepare_line_search(self, x: torch.Tensor):
+        """Make x feasible (constrained dofs at their bc values: every Newton update is then zero on them,
+        so every trial point of the line search is feasible too) and rebuild b_ext from the current loads."""
+        marker, g = fem._combine_bcs(self.L.V, self.bcs)
+        if marker is not None:
+            x.copy_(torch.where(marker.bool(), g, x))
+        self.total_energy().refresh()
 
 
 class KrylovSolver:
@@ -164,6 +199,12 @@ class NewtonSolver:
         self.iteration = 0
         self.krylov_iterations = 0
         self.history: list[float] = []
+        # globalisation: None = the plain update x -= relaxation_parameter * dx; "energy" = backtracking on
+        # the problem's potential (problem.energy). steps: the accepted s per iteration; energies: Pi at the
+        # start and after every accepted step
+        self.line_search: str | None = None
+        self.steps: list[float] = []
+        self.energies: list[float] = []
 
     def _converged(self, b: torch.Tensor) -> bool:
         # the reference's convergence check (asym_elasto_damage_model.cc:870-890)
@@ -175,11 +216,38 @@ class NewtonSolver:
                   f"r (rel) = {rel:e}(tol = {self.rtol})")
         return rel < self.rtol or self.residual < self.atol
 
+    def _energy_step(self, P, x: torch.Tensor, dx: torch.Tensor, b: torch.Tensor):
+        """x <- x - t dx with t = s * relaxation_parameter, s the first of 1, 1/2, .. 2^-10 whose trial point
+        has a finite energy that meets the Armijo condition Pi(x - t dx) <= Pi(x) - 1e-4 t slope, slope =
+        dot(b, dx) (b = grad Pi on the free dofs, so -slope is Pi's derivative along -dx). slope <= 0 (not a
+        descent direction: an indefinite tangent, or a Krylov solve that stopped early): the full step."""
+        slope = float(torch.dot(b, dx))
+        e0 = self.energies[-1]
+        x0 = x.clone()
+        s = 1.0
+        for _ in range(11):
+            t = s * self.relaxation_parameter
+            x.copy_(x0)
+            x.sub_(t * dx)
+            e = P.energy(x)
+            if slope <= 0.0 or (math.isfinite(e) and e <= e0 - 1e-4 * t * slope):
+                self.steps.append(s)
+                self.energies.append(e)
+                return
+            s *= 0.5
+        x.copy_(x0)
+        raise RuntimeError(f"energy line search failed at Newton iteration {self.iteration}: no step down to "
+                           f"2^-10 lowers Pi = {e0:e} (slope {slope:e})")
+
     def solve(self, u: fem.Function) -> tuple[int, bool]:
         P = self.problem
         x = u.x
-        if x.data_ptr() != P.u.x.data_ptr():
+        Pu = getattr(P, "u", None)  # (a bare problem object: F, J, matrix and, for the line search, energy)
+        if Pu is not None and x.data_ptr() != Pu.x.data_ptr():
             raise ValueError("solve(u) must be called with the problem's u")
+        if self.line_search not in (None, "energy"):
+            raise ValueError(f"line_search must be None or 'energy', not {self.line_search!r}")
+        form = getattr(P, "form", None) or (lambda x: None)
         b = torch.zeros_like(x)
         dx = torch.zeros_like(x)
         A = P.matrix()
@@ -187,16 +255,26 @@ class NewtonSolver:
         self.krylov_iterations = 0
         self.residual0 = 0.0
         self.history = []
-        P.form(x)
+        self.steps = []
+        self.energies = []
+        if self.line_search == "energy":
+            prepare = getattr(P, "prepare_line_search", None)
+            if prepare is not None:
+                prepare(x)
+            self.energies.append(P.energy(x))
+        form(x)
         P.F(x, b)
         converged = self._converged(b)
         while not converged and self.iteration < self.max_it:
             P.J(x, A)
             self.krylov_solver.set_operator(A)
             self.krylov_iterations += self.krylov_solver.solve(dx, b)
-            x.sub_(self.relaxation_parameter * dx)
+            if self.line_search is None:
+                x.sub_(self.relaxation_parameter * dx)
+            else:
+                self._energy_step(P, x, dx, b)
             self.iteration += 1
-            P.form(x)
+            form(x)
             P.F(x, b)
             if self.iteration == 1:
                 self.residual0 = float(torch.linalg.vector_norm(dx))

@@ -594,6 +594,44 @@ typedef struct {
  * (deformation-dependent) pressure and its unsymmetric tangent, interior-facet and Robin terms. */
 int fa_facet_load_apply(const fa_mesh* mesh, const fa_facet_load* load, double alpha, double* b, void* stream);
 
+/* ---- scalar functionals: energy and norm integrals (femasm_scalar.hip, fa_version() >= 107) ----
+ * dolfinx.fem.assemble_scalar for the integrands the library's forms define. The reference validates
+ * itself by displacement and energy errors; its energy is the integral of the potential whose derivative
+ * is the residual F_form (FEniCSx/mechanic2d/asym_ufl.py:78-81).
+ *
+ * fa_quadrature: the library's rule of degree qdeg (0 .. 12; 0 is the degree-1 rule) on the reference
+ * cell, HOST arrays, no device call: pts [nq][tdim], wts [nq]. With pts and wts both NULL only *nq is
+ * written; otherwise *nq holds the capacity of the arrays on entry (FA_E_ARG when short) and the point
+ * count on return. The rule every kernel here integrates with (make_quadrature). */
+int fa_quadrature(int32_t cell_type, int32_t qdeg, int32_t* nq, double* pts /* HOST */, double* wts /* HOST */);
+
+#define FA_FUNC_MEASURE 0       /* int 1 dx; rule qdeg, default max(1, the form estimate): exact on affine cells */
+#define FA_FUNC_STRAIN_ENERGY 1 /* int psi(grad u) dx of form's law on the rule of fa_assemble_vector's sigma term
+                                   (qdeg < 0: form->qdeg, and if that is < 0 the estimate; the damage kinds: always
+                                   their single point). FA_LINEAR_ELASTICITY: lam/2 tr(eps)^2 + mu eps:eps;
+                                   FA_NEO_HOOKEAN: mu/2 (I_C - 3) - mu ln J + lam/2 (ln J)^2 at F = I + grad u (a cell
+                                   with J <= 0 yields NaN or inf, which reaches the total); FA_ASYM_DAMAGE(_AD): the
+                                   reference's damage potential (MFEM/mechanic2d/asym_elasto_damage_model.cc:100-155)
+                                   with d the mean of the cell's three nodal values, the linear potential for d <= 0 */
+#define FA_FUNC_L2 2            /* int sum_i (w_i - g_i)^2 dx; rule qdeg, default 2 * degree */
+#define FA_FUNC_H1 3            /* int sum_ik (d_k w_i - G_ik)^2 dx; rule qdeg, default 2 * degree */
+/* fa_assemble_scalar: cell_out[c] = the integral over cell c (every cell visited once, one lane per cell,
+ * plain stores; NULL = kept in the workspace) and *total = their sum (NULL = no sum): per 256-cell tile a
+ * binary tree over the tile's entries, then the tile partials by one workgroup in a fixed order. No
+ * floating-point atomics: the total is bit-identical run to run and does not depend on the launch grid.
+ * w: the nodal field [nnodes][gdim] of FA_FUNC_L2 / FA_FUNC_H1 (ignored otherwise; the energies read
+ * form->u, which is required). g: FA_FUNC_L2 values [ncells][nq][gdim], FA_FUNC_H1 values
+ * [ncells][nq][gdim][gdim] at the rule's points, or NULL for zero. form may be NULL except for
+ * FA_FUNC_STRAIN_ENERGY. work: caller-owned, 8-byte aligned, at least fa_functional_work_bytes() bytes
+ * (host only); required when total is given. Asynchronous on `stream`; no allocation after the first call
+ * per (element, rule), which caches the tables. ncells == 0 writes +0.0 to *total with no cell launch.
+ * Null or short arguments: FA_E_ARG. Every supported element (P1 / P2 simplices, Q1 .. Q3); the damage
+ * kinds on P1 triangles only (FA_E_UNSUPPORTED otherwise). */
+int fa_functional_work_bytes(const fa_mesh* mesh, int64_t* bytes);
+int fa_assemble_scalar(const fa_mesh* mesh, const fa_form* form, int32_t kind, const double* w, const double* g,
+                       int32_t qdeg, double* cell_out /* [ncells] or NULL */, void* work, int64_t work_bytes,
+                       double* total /* device double or NULL */, void* stream);
+
 /* Measurement helper (not part of the reference interface): a 16-B-per-lane grid-stride stream
  * over n doubles (n even, 16-B aligned buffers) for the measured HBM peak beside the 8 TB/s spec
  * (SURVEY.md section 8(d)). mode 0: dst = src (copy), 1: dst = 1.0 (write only), 2: read src
