@@ -3,10 +3,10 @@
 Submodules mirror the reference's dolfinx surface: ``mesh`` (meshes in torch tensors),
 ``fem`` (function spaces, forms, Dirichlet BCs, create_matrix / assemble_matrix), ``la``
 (the BSR global matrix), ``io`` (XDMF meshes and mesh tags), ``mg`` (geometric multigrid
-preconditioner for ``nls.KrylovSolver``). Numerics run in libfemasm.so
+preconditioner for ``nls.KrylovSolver``), ``geometry`` (point location: ``bb_tree``, ``locate_points``). Numerics run in libfemasm.so
 (hand-written HIP for gfx950).
 """
-from . import fem, io, la, mesh, mg  # noqa: F401
+from . import fem, geometry, io, la, mesh, mg  # noqa: F401
 from ._lib import FemasmError, load  # noqa: F401
 
 __version__ = "0.1.0"

@@ -146,6 +146,17 @@ class fa_facet_load(ctypes.Structure):
     ]
 
 
+class fa_cell_grid(ctypes.Structure):
+    _fields_ = [
+        ("dims", ctypes.c_int32 * 3),
+        ("_pad", ctypes.c_int32),
+        ("lo", ctypes.c_double * 3),
+        ("inv_h", ctypes.c_double * 3),
+        ("bin_ptr", ctypes.c_void_p),
+        ("bin_cells", ctypes.c_void_p),
+    ]
+
+
 # exported symbols with their signatures; tests check every one against include/femasm.h
 P = ctypes.c_void_p
 I32, I64, D = ctypes.c_int32, ctypes.c_int64, ctypes.c_double
@@ -201,6 +212,8 @@ SIGNATURES = {
     "fa_quadrature": (ctypes.c_int, [I32, I32, P, P, P]),
     "fa_functional_work_bytes": (ctypes.c_int, [P, P]),
     "fa_assemble_scalar": (ctypes.c_int, [P, P, I32, P, P, I32, P, P, I64, P, P]),
+    "fa_locate_points": (ctypes.c_int, [P, P, I64, P, D, P, P, P]),
+    "fa_eval_points": (ctypes.c_int, [P, P, I32, I64, P, P, P, P, P]),
     "fa_hbm_probe": (ctypes.c_int, [I32, P, P, I64, P]),
 }
 

@@ -153,15 +153,21 @@ class FunctionSpace:
         if self._x is None and self.mesh.structured is not None and self.degree > 1:
             self._x = _structured_node_coordinates(self.mesh, self.degree)
         if self._x is None:
-            m = self.mesh
-            X = reference_nodes(m.cell_type, self.degree)
-            Psi = torch.tensor(_geometry_basis(m.cell_type, X), dtype=torch.float64, device=m.device)  # [nn, nv]
-            xv = m.x[m.cells.to(torch.int64)]  # [nc, nv, gdim]
-            xn = torch.einsum("kv,cvd->ckd", Psi, xv)
-            out = torch.zeros((self.num_nodes, m.gdim), dtype=torch.float64, device=m.device)
-            out[self.dofmap.to(torch.int64).reshape(-1)] = xn.reshape(-1, m.gdim)
-            self._x = out
+            self._x = self._mapped_node_coordinates()
         return self._x
+
+    def _mapped_node_coordinates(self) -> torch.Tensor:
+        """The geometry map of the mesh's CURRENT vertices applied to the reference nodes [num_nodes, gdim]
+        (not cached; the lattice shortcut of ``tabulate_dof_coordinates`` describes the generator's box, not
+        a mesh whose vertices were moved afterwards)."""
+        m = self.mesh
+        X = reference_nodes(m.cell_type, self.degree)
+        Psi = torch.tensor(_geometry_basis(m.cell_type, X), dtype=torch.float64, device=m.device)  # [nn, nv]
+        xv = m.x[m.cells.to(torch.int64)]  # [nc, nv, gdim]
+        xn = torch.einsum("kv,cvd->ckd", Psi, xv)
+        out = torch.zeros((self.num_nodes, m.gdim), dtype=torch.float64, device=m.device)
+        out[self.dofmap.to(torch.int64).reshape(-1)] = xn.reshape(-1, m.gdim)
+        return out
 
     # native objects -------------------------------------------------------------------
     def _fa_mesh(self) -> _lib.fa_mesh:
@@ -297,11 +303,22 @@ class Function:
     def array(self) -> torch.Tensor:
         return self.x
 
-    def interpolate(self, fn):
+    def eval(self, x, cells=None, grad: bool = False):
+        """dolfinx ``Function.eval(x, cells)``: values [n, bs] at the physical points x [n, gdim] (``eval_points``;
+        cells None: the points are located first)."""
+        return eval_points(self, x, cells=cells, grad=grad)
+
+    def interpolate(self, fn, missing: str = "raise"):
         """Nodal interpolation: fn(x[gdim, n]) -> values [bs, n] (dolfinx convention), or an
         ``Expression`` evaluated at the single interpolation point of a DG0 space
-        (FEniCSx/mechanic2d/asym_elasto_damage_model.cc:926-927: ``stress->interpolate(expr)``)."""
+        (FEniCSx/mechanic2d/asym_elasto_damage_model.cc:926-927: ``stress->interpolate(expr)``), or a
+        ``Function`` on another mesh or space of the same block size: this space's nodes (a DG0 space: its
+        cell midpoints) are located in the other function's mesh and take its values there. missing: what a
+        node outside that mesh does, "raise" (ValueError with their number), "keep" (its value stays) or
+        "nan"."""
         V = self.function_space
+        if isinstance(fn, Function):
+            return self._interpolate_function(fn, missing)
         if isinstance(fn, Expression):
             if V.family not in ("DG", "Discontinuous Lagrange") or V.degree != 0:
                 raise ValueError("interpolating an Expression needs a DG0 space")
@@ -319,6 +336,35 @@ class Function:
         vals = fn(xn.T)
         vals = torch.as_tensor(vals, dtype=torch.float64, device=xn.device).reshape(V.bs, -1)
         self.x = vals.T.contiguous().reshape(-1)
+
+    def _interpolate_function(self, other: "Function", missing: str):
+        if missing not in ("raise", "keep", "nan"):
+            raise ValueError(f"missing must be 'raise', 'keep' or 'nan', not {missing!r}")
+        V, W = self.function_space, other.function_space
+        if V.bs != W.bs:
+            raise ValueError(f"block size {V.bs} != the other function's {W.bs}")
+        if V.mesh.device != W.mesh.device:
+            raise ValueError("the two functions live on different devices")
+        if V.mesh.gdim != W.mesh.gdim:
+            raise ValueError("the two meshes have different dimensions")
+        if V.family in ("DG", "Discontinuous Lagrange"):
+            m = V.mesh
+            Psi = torch.tensor(_geometry_basis(m.cell_type, interpolation_points(m.cell_type)), dtype=torch.float64,
+                               device=m.device)
+            xn = torch.einsum("qv,cvd->cqd", Psi, m.x[m.cells.to(torch.int64)]).reshape(-1, m.gdim)
+        else:
+            xn = V._mapped_node_coordinates()  # (the mesh's current vertices, whatever generated it)
+        from . import geometry
+
+        cells, X = geometry.locate_points(W.mesh, xn)
+        vals = eval_points(other, xn, cells=cells, X=X)
+        found = cells >= 0
+        nmiss = int((~found).sum())
+        if nmiss and missing == "raise":
+            raise ValueError(f"interpolate: {nmiss} of {xn.shape[0]} nodes lie outside the other function's mesh")
+        if nmiss and missing == "keep":
+            vals = torch.where(found[:, None], vals, self.x.view(-1, V.bs))
+        self.x = vals.contiguous().reshape(-1)
 
 
 class Constant:
@@ -1757,6 +1803,88 @@ def _space_basis_gradients(ct, p: int, X: np.ndarray) -> np.ndarray:
 
 def _field(w):
     return w.x if isinstance(w, Function) else w
+
+
+# ---------------------------------------------------------------------------------- evaluation at points
+def _eval_points_host(V: FunctionSpace, w: torch.Tensor, cells: torch.Tensor, X: torch.Tensor, grad: bool):
+    """k_eval_points in torch (what a mesh on the CPU runs): (val [n, bs], grad [n, bs, gdim] or None)."""
+    m = V.mesh
+    bs, gd = V.bs, m.gdim
+    found = cells >= 0
+    c = cells.to(torch.int64).clamp(min=0)
+    Xs = torch.where(found[:, None], X, torch.zeros_like(X))
+    Xn = Xs.cpu().numpy()
+    dev = m.device
+    phi = torch.as_tensor(_space_basis(m.cell_type, V.degree, Xn), device=dev)  # [n, nn]
+    wc = w.view(-1, bs)[V.dofmap.to(torch.int64)[c]]  # [n, nn, bs]
+    nan = float("nan")
+    val = torch.einsum("na,nar->nr", phi, wc)
+    val = torch.where(found[:, None], val, torch.full_like(val, nan))
+    if not grad:
+        return val, None
+    dphi = torch.as_tensor(_space_basis_gradients(m.cell_type, V.degree, Xn), device=dev)  # [n, nn, td]
+    gg = torch.as_tensor(_geometry_gradients(m.cell_type, Xn), device=dev)  # [n, nv, td]
+    xv = m.x[m.cells.to(torch.int64)[c]]
+    xv = xv - xv[:, :1]
+    J = torch.einsum("nvi,nvk->nik", xv, gg)
+    R = torch.einsum("nar,nak->nrk", wc, dphi)
+    g = torch.einsum("nrk,nkj->nrj", R, torch.linalg.inv(J)) if J.shape[0] else R
+    return val, torch.where(found[:, None, None], g, torch.full_like(g, nan))
+
+
+def eval_points(u, x=None, cells=None, X=None, grad: bool = False, V: FunctionSpace | None = None):
+    """A finite-element field at arbitrary physical points: values [n, bs], and with ``grad=True`` also the
+    gradients [n, bs, gdim] (d u_r / d x_j), at the points x [n, gdim]. u: a ``Function``, or a nodal tensor
+    with its space ``V``; block size 1 to 3. The points are located with ``geometry.locate_points`` unless
+    ``cells`` and ``X`` (its two results) are given; ``cells`` alone pulls the points back into those cells
+    (dolfinx ``Function.eval(x, cells)``). Rows whose point no cell holds (cell -1) are NaN.
+    A GPU mesh runs k_eval_points (fa_eval_points: the basis evaluated on the device at each point's own
+    reference coordinates, one lane per point); a CPU mesh the same definition in torch. A DG0 space returns
+    ``u.x[cell]``; its gradient raises."""
+    from . import geometry
+
+    if isinstance(u, Function):
+        V, w = u.function_space, u.x
+    else:
+        if V is None:
+            raise ValueError("a nodal tensor needs its space: eval_points(w, x, V=V)")
+        w = u
+    m = V.mesh
+    dev, gd, bs = m.device, m.gdim, V.bs
+    if not 1 <= bs <= 3:
+        raise ValueError(f"eval_points: block size {bs} outside 1 .. 3")
+    if w.dtype != torch.float64 or w.numel() != V.num_dofs or not w.is_contiguous() or w.device != dev:
+        raise ValueError(f"u must be a contiguous float64 vector of {V.num_dofs} entries on {dev}")
+    if cells is None or X is None:
+        if x is None:
+            raise ValueError("eval_points needs the points x, or cells and X")
+        x = torch.as_tensor(x, dtype=torch.float64, device=dev).reshape(-1, gd).contiguous()
+        if cells is None:
+            cells, X = geometry.locate_points(m, x)
+        else:
+            cells = torch.as_tensor(cells, device=dev).to(torch.int32).reshape(-1).contiguous()
+            X = geometry.pull_back(m, x, cells)
+    cells = torch.as_tensor(cells, device=dev).to(torch.int32).reshape(-1).contiguous()
+    X = torch.as_tensor(X, dtype=torch.float64, device=dev).reshape(-1, gd).contiguous()
+    n = cells.numel()
+    if X.shape[0] != n:
+        raise ValueError(f"{n} cells but {X.shape[0]} reference points")
+    if V.family in ("DG", "Discontinuous Lagrange"):
+        if grad:
+            raise ValueError("a DG0 function has no gradient to evaluate")
+        found = cells >= 0
+        val = w.view(-1, bs)[cells.to(torch.int64).clamp(min=0)]
+        return torch.where(found[:, None], val, torch.full_like(val, float("nan")))
+    if dev.type != "cuda":
+        val, g = _eval_points_host(V, w, cells, X, grad)
+        return (val, g) if grad else val
+    val = torch.empty((n, bs), dtype=torch.float64, device=dev)
+    g = torch.empty((n, bs, gd), dtype=torch.float64, device=dev) if grad else None
+    if n:
+        fm = V._fa_mesh()
+        _lib.check(_lib.load().fa_eval_points(ctypes.byref(fm), w.data_ptr(), bs, n, cells.data_ptr(), X.data_ptr(),
+                                              val.data_ptr(), _lib.ptr(g), _lib.stream_handle(dev)), "fa_eval_points")
+    return (val, g) if grad else val
 
 
 class Measure:

@@ -632,6 +632,61 @@ int fa_assemble_scalar(const fa_mesh* mesh, const fa_form* form, int32_t kind, c
                        int32_t qdeg, double* cell_out /* [ncells] or NULL */, void* work, int64_t work_bytes,
                        double* total /* device double or NULL */, void* stream);
 
+/* ---- point location and evaluation at arbitrary points (femasm_points.hip, fa_version() >= 108) ----
+ * dolfinx.geometry.bb_tree + compute_collisions_points + compute_colliding_cells, and Function.eval: which cell
+ * holds a physical point, where in the cell, and a finite-element field's value and gradient there. The
+ * reference compares displacements computed on different meshes by matching dof coordinates (the IN_COMP block
+ * of FEniCSx/mechanic2d/asym_elasto_damage_model.cc sorts them and throws when a node has no twin; doc.tex,
+ * figure ref2_mesh_difference); with these two calls the meshes need not share nodes or cells.
+ *
+ * The plan (host-built once per mesh and coordinates, all DEVICE arrays; femasm.geometry.bb_tree): a uniform
+ * grid over the box of the cells' PADDED bounding boxes. A cell is listed in every bin its padded box meets;
+ * the padding must cover the tolerance, i.e. every point a cell accepts lies in that cell's padded box
+ * (femasm pads by 1e-6 of the box diagonal and requires tol <= a quarter of that factor). */
+typedef struct {            /* uniform grid over the mesh's (padded) bounding box */
+  int32_t dims[3];          /* bins per axis (entries d >= gdim are 1) */
+  int32_t _pad;
+  double lo[3], inv_h[3];   /* bin of x along d: clamp(floor((x[d]-lo[d])*inv_h[d]), 0, dims[d]-1) */
+  const int64_t* bin_ptr;   /* [nbins+1], bin index = (k*dims[1]+j)*dims[0]+i */
+  const int32_t* bin_cells; /* cells whose padded bounding box meets the bin, ASCENDING cell id per bin */
+} fa_cell_grid;
+
+/* cell[i] = the SMALLEST id among the cells that accept point x[i] (unique on shared vertices, edges and
+ * faces, whatever the grid), X[i] = the point's reference coordinates in that cell; no cell accepts:
+ * cell[i] = -1 and X[i] = NaN. One lane per point: with t_d = (x[d] - lo[d]) * inv_h[d], a point with some
+ * t_d outside [0, dims[d]] (outside the grid's box; a NaN or infinite coordinate) is rejected without reading
+ * a bin; otherwise the lane walks its bin's cells in stored order and stops at the first that accepts.
+ *
+ * Acceptance rule (the definition; femasm.geometry's host path applies the same one). Vertex 0 is subtracted
+ * first: e_v = x_v - x_v0, dx = x - x_v0.
+ *   triangles, tetrahedra   J = [e_1 .. e_tdim]; X = adj(J) dx / det J (cofactor form, either sign of det J:
+ *       mirrored cells are cells); lambda_0 = 1 - sum X, lambda_k = X_(k-1); accept when every lambda_i >= -tol.
+ *   quadrilaterals, hexahedra   Newton on the Q1 map from the centre X = 1/2: r = sum_v psi_v(X) e_v - dx,
+ *       J = sum_v e_v (x) grad psi_v(X), X <- X - adj(J) r / det J; at most 12 steps; converged when a step has
+ *       |dX|_inf <= 1e-12 (an affine cell: the first step lands, the second confirms). A step whose det J has
+ *       not the sign of det J at the centre, or that leaves [-1, 2]^tdim, rejects the CELL (the walk goes on),
+ *       as does running out of steps. Accept when converged and -tol <= X_d <= 1 + tol for every d.
+ * tol is in reference coordinates (femasm: 1e-10). mesh->geom / x are read (mesh->cells only for the
+ * argument check). Entries of bin_cells outside [0, ncells) are skipped, never dereferenced.
+ * Asynchronous, no allocation, no atomics, 64-bit index arithmetic; npts == 0 launches nothing. Null or
+ * short arguments, a grid with a dimension < 1 or tol < 0: FA_E_ARG; an unsupported element: FA_E_UNSUPPORTED. */
+int fa_locate_points(const fa_mesh* mesh, const fa_cell_grid* grid, int64_t npts, const double* x /*[npts][gdim]*/,
+                     double tol, int32_t* cell /*[npts]*/, double* X /*[npts][gdim]*/, void* stream);
+
+/* val[i][r] = sum_a phi_a(X_i) w[node_a][r] and grad[i][r][j] = sum_a w[node_a][r] (grad_X phi_a(X_i) . J(X_i)^-1)_j
+ * in cell cell[i], with the space's Lagrange basis evaluated on the device at each point's own X (P1 / P2
+ * simplices: closed form in the barycentrics, basix node order; Q1 .. Q3: products of 1-D Lagrange polynomials
+ * on the element's own nodes, equispaced for p <= 2 and GLL for p = 3, the node positions and the node <->
+ * lattice map uploaded once per element from the host definition) and J from the P1 / Q1 geometry at X,
+ * inverted in cofactor form. mesh->cells / degree / nn are the space's dofmap; w [nnodes][bs], bs 1 .. 3 (any
+ * block size, not only gdim). Rows with cell[i] < 0 (or >= ncells) get NaN and read nothing. Either output
+ * may be NULL, not both. One lane per point, no atomics: deterministic. Asynchronous; no allocation after the
+ * first call per tensor element, which caches that table. Every element fa_eval_cells takes, affine or not.
+ * npts == 0 launches nothing. Null arguments, bs outside 1 .. 3: FA_E_ARG; unsupported element: FA_E_UNSUPPORTED. */
+int fa_eval_points(const fa_mesh* mesh /* its cells/degree/nn are the space's dofmap */, const double* w /*[nnodes][bs]*/,
+                   int32_t bs /*1..3*/, int64_t npts, const int32_t* cell, const double* X,
+                   double* val /*[npts][bs] or NULL*/, double* grad /*[npts][bs][gdim] or NULL*/, void* stream);
+
 /* Measurement helper (not part of the reference interface): a 16-B-per-lane grid-stride stream
  * over n doubles (n even, 16-B aligned buffers) for the measured HBM peak beside the 8 TB/s spec
  * (SURVEY.md section 8(d)). mode 0: dst = src (copy), 1: dst = 1.0 (write only), 2: read src
