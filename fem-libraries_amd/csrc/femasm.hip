@@ -562,6 +562,19 @@ __device__ __forceinline__ T damage_potential(const T (&e)[4], double l, double 
   const double i1 = ad_val(I1), i2 = ad_val(I2);
   if (i1 > limit || i2 > limit || i1 < mlimit || i2 < mlimit) {
     const T delta = I1 * I1 + 4.0 * I2;
+    // Double eigenvalue, the hand hook's r < limit: sqrt is not differentiable at 0 (the dual
+    // passes would take ad_inv(0): inf - inf), and psi is smooth there. |I1| > limit > r in this
+    // branch, so ev1, ev2 and I1 share one sign and ev1^2 + ev2^2 = (I1^2 + delta) / 2:
+    // psi = (1 - alpha d) psi_linear, no square root taken. I1^2 + 4 I2 cancels: on a strain with
+    // roundoff it is +-ulp(I1^2) where the eigenvalues coincide (r = 2^-26 |I1|, or the square root of a
+    // negative number), and the dual passes would then lose |I1| / r of their digits; so the test also
+    // takes delta in the form that does not cancel, (e11 - e22)^2 + 4 e21 e12.
+    const double dif = ad_val(e[0]) - ad_val(e[3]);
+    const double dv = fmin(ad_val(delta), dif * dif + 4.0 * ad_val(e[1]) * ad_val(e[2]));
+    if (sqrt(fmax(0.0, dv)) < limit) {
+      const double alpha = i1 >= 0.0 ? 1.0 : 0.0;
+      return (1.0 - alpha * d) * ((0.5 * l) * (I1 * I1) + (0.5 * m) * (I1 * I1 + delta));
+    }
     const T r = ad_sqrt(delta);
     const T ev1 = 0.5 * (I1 + r), ev2 = 0.5 * (I1 - r);
     const double alpha1 = ad_val(ev1) >= 0.0 ? 1.0 : 0.0, alpha2 = ad_val(ev2) >= 0.0 ? 1.0 : 0.0;

@@ -2099,22 +2099,32 @@ def assemble_scalar_host(M):
             I1, I2 = e11 + e22, e12 * e12 - e11 * e22
             with torch.no_grad():
                 nz = (I1.abs() > 1e-12) | (I2.abs() > 1e-12)
-            delta = torch.where(nz, I1 * I1 + 4.0 * I2, torch.ones_like(I1))
-            r = torch.sqrt(delta)
+            dl = I1 * I1 + 4.0 * I2
+            with torch.no_grad():
+                # the double eigenvalue (the hand hook's r < 1e-12): sqrt has no derivative at 0, psi has
+                # (dl cancels to +-ulp(I1^2) there on a strain with roundoff: the test also takes the form that does not)
+                dl2 = (e11 - e22) * (e11 - e22) + 4.0 * e12 * e12
+                dbl = nz & (torch.sqrt(torch.minimum(dl, dl2).clamp_min(0.0)) < 1e-12)
+                gen = nz & ~dbl
+            r = torch.sqrt(torch.where(gen, dl, torch.ones_like(I1)))
             ev1, ev2 = 0.5 * (I1 + r), 0.5 * (I1 - r)
             with torch.no_grad():
                 a1, a2 = (ev1 >= 0).to(gu.dtype), (ev2 >= 0).to(gu.dtype)
                 al = ((ev1 + ev2) >= 0).to(gu.dtype)
+                ai = (I1 >= 0).to(gu.dtype)
             p_dam = 0.5 * (1.0 - al * d) * lam * (I1 * I1) + mu * ((1.0 - a1 * d) * ev1 * ev1 + (1.0 - a2 * d) * ev2 * ev2)
+            # |I1| > 1e-12 > r there: ev1, ev2 and I1 share a sign and ev1^2 + ev2^2 = (I1^2 + delta) / 2
+            p_dbl = (1.0 - ai * d) * (0.5 * lam * (I1 * I1) + 0.5 * mu * (I1 * I1 + dl))
             p_null = (1.0 - d) * (0.5 * lam * (I1 * I1) + mu * (e11 * e11 + e22 * e22 + 2.0 * e12 * e12))
-            psi = torch.where(d > 0, torch.where(nz, p_dam, p_null), psi)
+            psi = torch.where(d > 0, torch.where(gen, p_dam, torch.where(dbl, p_dbl, p_null)), psi)
             with torch.no_grad():
                 I1a = gua[..., 0, 0] + gua[..., 1, 1]
                 e12a = 0.5 * (gua[..., 0, 1] + gua[..., 1, 0])
                 da = I1a * I1a + 4.0 * (e12a * e12a + gua[..., 0, 0] * gua[..., 1, 1])
                 eva = 0.5 * (I1a + da / r)  # r's error is bounded by eps * da / (2 r), and r <= da / r
                 pd = 0.5 * lam.abs() * I1a * I1a + 2.0 * mu.abs() * eva * eva
-                pm = torch.where(d > 0, torch.where(nz, pd, pm), pm)
+                pb = 0.5 * lam.abs() * I1a * I1a + 0.5 * mu.abs() * (I1a * I1a + da)
+                pm = torch.where(d > 0, torch.where(gen, pd, torch.where(dbl, pb, pm)), pm)
     return (wd * psi).sum(1), (wd * pm).sum(1).detach()
 
 
