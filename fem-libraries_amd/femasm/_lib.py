@@ -214,7 +214,15 @@ SIGNATURES = {
     "fa_assemble_scalar": (ctypes.c_int, [P, P, I32, P, P, I32, P, P, I64, P, P]),
     "fa_locate_points": (ctypes.c_int, [P, P, I64, P, D, P, P, P]),
     "fa_eval_points": (ctypes.c_int, [P, P, I32, I64, P, P, P, P, P]),
+    "fa_bcsr_mult": (ctypes.c_int, [I64, I64, I32, I32, P, P, P, P, I32, P, P]),
+    "fa_bcsr_product": (ctypes.c_int, [I64, I32, I32, I32, P, I64, P, P, P, I64, P, I64, P, P]),
+    "fa_csr_row_max": (ctypes.c_int, [I64, P, P, P, P, I64, P, P]),
     "fa_hbm_probe": (ctypes.c_int, [I32, P, P, I64, P]),
+}
+# entry points whose names carry a digit (the header scan that SIGNATURES is checked against reads
+# lower-case names only); bound like the others
+SIGNATURES_NUMBERED = {
+    "fa_cheb_step6": (ctypes.c_int, [I64, P, P, P, D, D, P, P, P]),
 }
 
 _lib = None
@@ -231,7 +239,7 @@ def load(path: str | None = None):
             f"{path} is missing: build it with `make -C {CSRC}` (hipcc --offload-arch=gfx950) "
             "or __graft_entry__.build(); femasm has no CPU fallback")
     L = ctypes.CDLL(path)
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in {**SIGNATURES, **SIGNATURES_NUMBERED}.items():
         fn = getattr(L, name, None)
         if fn is None:
             if os.path.abspath(path) == os.path.abspath(LIB_PATH):

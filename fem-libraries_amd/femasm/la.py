@@ -159,3 +159,96 @@ class MatrixCSR:
             r0 = self.parts[part][0]
             _lib.check(L.fa_bsr_block_diag(ctypes.byref(fb), out[r0:].data_ptr(), sh), "fa_bsr_block_diag")
         return out
+
+
+class BlockCSR:
+    """Block-CSR matrix with rectangular row-major blocks: ``indptr`` int64 [nrows+1], ``indices`` int32
+    [nblocks] block columns, ``data`` float64 [nblocks, br, bc], ``num_block_cols`` block columns. Holds the
+    prolongators of ``mg.SmoothedAggregation``, their stored transposes and its coarse matrices (square,
+    3- or 6-dof nodes). ``mult`` is fa_bcsr_mult on the device and the same gather in torch on the CPU."""
+
+    def __init__(self, indptr: torch.Tensor, indices: torch.Tensor, data: torch.Tensor, num_block_cols: int):
+        if data.dim() != 3 or data.dtype != torch.float64 or data.shape[0] != indices.shape[0]:
+            raise ValueError("data must be a float64 tensor [nblocks, br, bc]")
+        self.indptr = indptr.to(torch.int64).contiguous()
+        self.indices = indices.to(torch.int32).contiguous()
+        self.data = data.contiguous()
+        self.br, self.bc = int(data.shape[1]), int(data.shape[2])
+        self.num_block_cols = int(num_block_cols)
+        self._rows = self._diag = None
+
+    @property
+    def bs(self) -> int:
+        if self.br != self.bc:
+            raise ValueError(f"a matrix of {self.br} x {self.bc} blocks has no single block size")
+        return self.br
+
+    @property
+    def num_block_rows(self) -> int:
+        return int(self.indptr.shape[0] - 1)
+
+    @property
+    def num_blocks(self) -> int:
+        return int(self.indices.shape[0])
+
+    @property
+    def shape(self):
+        return (self.num_block_rows * self.br, self.num_block_cols * self.bc)
+
+    @property
+    def nnz(self) -> int:
+        return self.num_blocks * self.br * self.bc
+
+    def block_rows(self) -> torch.Tensor:
+        """Block row of every stored block, int64 [nblocks] (cached)."""
+        if self._rows is None:
+            self._rows = torch.repeat_interleave(torch.arange(self.num_block_rows, device=self.indices.device),
+                                                 self.indptr[1:] - self.indptr[:-1])
+        return self._rows
+
+    def to_scipy(self):
+        """scipy.sparse.bsr_matrix on the host (test / debug helper)."""
+        import scipy.sparse as sp
+
+        return sp.bsr_matrix((self.data.detach().cpu().numpy(), self.indices.cpu().numpy(), self.indptr.cpu().numpy()),
+                             shape=self.shape, blocksize=(self.br, self.bc))
+
+    def mult(self, x: torch.Tensor, y: torch.Tensor | None = None, add: bool = False) -> torch.Tensor:
+        """y (+)= B x; x [num_block_cols * bc], y [num_block_rows * br]."""
+        if y is None:
+            if add:
+                raise ValueError("add needs y")
+            y = torch.empty(self.shape[0], dtype=torch.float64, device=x.device)
+        for v, n in ((x, self.shape[1]), (y, self.shape[0])):
+            if v.dtype != torch.float64 or v.numel() != n or not v.is_contiguous() or v.device != self.data.device:
+                raise ValueError(f"BlockCSR.mult vectors must be contiguous float64 of {self.shape[1]} and "
+                                 f"{self.shape[0]} entries on {self.data.device}")
+        if x.device.type != "cuda":
+            prod = torch.bmm(self.data, x.view(-1, self.bc)[self.indices.to(torch.int64)].unsqueeze(2)).squeeze(2)
+            out = y.view(-1, self.br) if add else y.view(-1, self.br).zero_()
+            out.index_add_(0, self.block_rows(), prod)  # in stored order
+            return y
+        from . import _lib
+
+        _lib.check(_lib.load().fa_bcsr_mult(self.num_block_rows, self.num_block_cols, self.br, self.bc,
+                                            self.indptr.data_ptr(), self.indices.data_ptr(), self.data.data_ptr(),
+                                            x.data_ptr(), int(bool(add)), y.data_ptr(), _lib.stream_handle(x.device)),
+                   "fa_bcsr_mult")
+        return y
+
+    def diagonal_block_slots(self) -> torch.Tensor:
+        """Slot of the diagonal block of every row (-1 if absent), int64 (cached)."""
+        if self._diag is None:
+            rows = self.block_rows()
+            hit = rows == self.indices.to(torch.int64)
+            out = torch.full((self.num_block_rows,), -1, dtype=torch.int64, device=self.indices.device)
+            out[rows[hit]] = torch.nonzero(hit).reshape(-1)
+            self._diag = out
+        return self._diag
+
+    def block_diagonal(self) -> torch.Tensor:
+        """Diagonal blocks [nrows, bs, bs] (zeros where a row has none)."""
+        slots = self.diagonal_block_slots()
+        D = self.data[slots.clamp(min=0)]
+        D[slots < 0] = 0.0
+        return D

@@ -22,6 +22,11 @@ vertex ``nv + e``, the numbering of the degree-2 nodes (``fem._generic_dofmap``)
 ``EdgeTransfer``, ``fa_prolong_edges`` / ``fa_restrict_edges`` in femasm_refine.hip) is again both the
 p- and the h-transfer. The hierarchy is the chain of ``mesh.parent`` (``plan_refined_hierarchy``);
 everything from ``update()`` down is shared with the lattice path.
+
+A mesh with neither a lattice nor parents is served by ``SmoothedAggregation``: below the degree-1 level its
+levels are algebraic (``femasm.amg``: MIS(2) aggregates, rigid-body modes, a smoothed prolongator and Galerkin
+products over ``fa_bcsr_product`` / ``fa_bcsr_mult`` in femasm_amg.hip). Smoother, eigenvalue estimate, coarse
+solve and V-cycle are the same code (``_VCycle``).
 """
 from __future__ import annotations
 
@@ -32,7 +37,7 @@ from dataclasses import dataclass
 import numpy as np
 import torch
 
-from . import _lib, fem
+from . import _lib, amg, fem
 from . import mesh as fmesh
 from .mesh import CellType
 
@@ -345,6 +350,10 @@ def cheb_step(Dinv: torch.Tensor, b: torch.Tensor, Ax: torch.Tensor | None, c_d:
             raise ValueError(f"fa_cheb_step vectors must be contiguous float64 of {nn * bs} entries on {Dinv.device}")
     if Dinv.dtype != torch.float64 or not Dinv.is_contiguous() or Dinv.shape[2] != bs:
         raise ValueError("Dinv must be a contiguous float64 [nnodes, bs, bs] tensor")
+    if bs == 6:  # the 6-dof nodes of the algebraic levels in 3-D
+        _lib.check(_lib.load().fa_cheb_step6(nn, Dinv.data_ptr(), b.data_ptr(), _lib.ptr(Ax), float(c_d), float(c_r),
+                                             d.data_ptr(), x.data_ptr(), _lib.stream_handle(x.device)), "fa_cheb_step6")
+        return
     _lib.check(_lib.load().fa_cheb_step(nn, bs, Dinv.data_ptr(), b.data_ptr(), _lib.ptr(Ax), float(c_d), float(c_r),
                                         d.data_ptr(), x.data_ptr(), _lib.stream_handle(x.device)), "fa_cheb_step")
 
@@ -362,105 +371,94 @@ def chebyshev_coefficients(lo: float, hi: float, degree: int) -> list:
     return out
 
 
-class GeometricMultigrid:
-    """One V-cycle of geometric multigrid as a fixed, symmetric positive definite preconditioner
-    (``apply(r, z)`` / ``update()``: the interface of ``nls.KrylovSolver.set_preconditioner``).
+class _VCycle:
+    """What the multigrid preconditioners share: the level records, the rediscretised degree-1 level below
+    a degree-2 space, the block-Jacobi / Chebyshev smoother with its eigenvalue estimate, the dense inverse
+    of the coarsest level and the V-cycle. A level ``L`` has ``bs`` dofs per node, ``ndofs`` dofs, an
+    operator ``A`` (``mult`` / ``block_diagonal``), a constraint ``marker`` or None, the scratch vectors
+    ``r, z, d, t`` and, unless it is the last, the ``transfer`` to the next level."""
 
-    a: the Jacobian form on a structured mesh (LinearElasticity / AsymDamage / NeoHookean); bcs, diagonal
-    as ``fem.assemble_matrix``. Level 0 is the form's own space with ``fine_operator`` (anything with
-    ``mult(x, y)`` and ``block_diagonal()``) or ``fem.JacobianOperator(a, bcs, diagonal)``; a degree-2
-    space is followed by degree 1 on the same mesh; further levels halve every ``n`` (``plan_hierarchy``).
-    Coarse forms are rediscretised with the same form class: per-cell coefficients are the mean over the
-    child cells, the nodal state is injected, a coarse node is constrained where its coinciding fine node
-    is; coarse operators are assembled (``fem.assemble_matrix``). The smoother is Chebyshev of degree
-    ``smoother_degree`` over block-Jacobi on [0.1, 1.1] x the estimated largest eigenvalue of D^-1 A,
-    the same polynomial before and after the coarse correction. A coarsest level of at most
-    ``coarse_dofs`` dofs is inverted densely at ``update()``, a larger one gets a fixed Chebyshev
-    polynomial of degree 8.
-
-    On a mesh without a lattice (``mesh.structured is None``: triangles and tetrahedra) the levels follow
-    ``plan_refined_hierarchy``: degree 2 to degree 1 on the same mesh, then degree 1 on every
-    ``mesh.parent`` that ``mesh.refine`` left behind. The transfer is an ``EdgeTransfer``, injection takes
-    the first ``ncoarse`` nodes, the coarse marker is the leading slice of the fine one, the parent of cell
-    ``j`` is ``j >> tdim``; ``levels`` reports ``n = None``.
-
-    ``update()`` must follow every change of the state (``KrylovSolver.set_operator`` calls it); the
-    first ``apply`` runs it if nobody has. ``levels``: [(degree, n, num_dofs, kind)];
-    ``operator_complexity``: stored matrix entries of all levels over those of the level-0 matrix."""
-
-    def __init__(self, a, bcs=None, diagonal: float = 1.0, fine_operator=None, smoother_degree: int = 2,
-                 coarse_dofs: int = 6000, max_levels: int | None = None):
+    def _init_common(self, a, bcs, diagonal, smoother_degree, coarse_dofs):
         if not isinstance(a, fem.LinearElasticity):
             raise TypeError("expected a femasm form descriptor (LinearElasticity, AsymDamage, ...)")
         if smoother_degree < 1:
             raise ValueError("smoother_degree must be at least 1")
-        V = a.V
-        refined = V.mesh.structured is None
-        table = (plan_refined_hierarchy if refined else plan_hierarchy)(V, coarse_dofs, max_levels)
-        if V.bs != V.mesh.gdim:
-            raise ValueError("the form's space must be a vector Lagrange space (bs = gdim)")
-        self.a, self.V = a, V
+        self.a, self.V = a, a.V
         self.bcs = list(bcs or [])
         self.diagonal = float(diagonal)
         self.smoother_degree = int(smoother_degree)
         self.coarse_dofs = int(coarse_dofs)
         self.updates = 0
-        m, dev, bs = V.mesh, V.mesh.device, V.bs
-        simplex = fem.is_simplex(m.cell_type)
-        st = m.structured
         self._levels = []
-        for li, (p, n) in enumerate(table):
-            L = _Level()
-            L.degree, L.n = p, (None if refined else n)
-            if li == 0:
-                L.V, L.a = V, a
-                L.marker, _ = fem._combine_bcs(V, self.bcs, with_g=False)
-                L.A = fine_operator if fine_operator is not None else \
-                    fem.JacobianOperator(a, bcs=self.bcs, diagonal=self.diagonal)
-                L.kind = "matrix-free" if isinstance(L.A, fem.JacobianOperator) else "operator"
+        self._gen = torch.Generator(device=a.V.mesh.device)
+        self._nnz0 = None
+
+    def _fine_level(self, fine_operator):
+        """Level 0: the form's own space with ``fine_operator`` or the matrix-free Jacobian."""
+        L = _Level()
+        V = self.V
+        L.degree, L.n = V.degree, None
+        L.V, L.a = V, self.a
+        L.marker, _ = fem._combine_bcs(V, self.bcs, with_g=False)
+        L.A = fine_operator if fine_operator is not None else \
+            fem.JacobianOperator(self.a, bcs=self.bcs, diagonal=self.diagonal)
+        L.kind = "matrix-free" if isinstance(L.A, fem.JacobianOperator) else "operator"
+        return self._add_level(L, V.bs, V.num_dofs)
+
+    def _geometric_level(self, F, n, refined: bool):
+        """The assembled degree-1 level below level F: on the lattice ``n`` (``n == F.n``: F's own mesh,
+        below a degree-2 level) or, refined, on the mesh ``n`` (F's own below degree 2, else its parent)."""
+        L = _Level()
+        m, dev, bs = self.V.mesh, self.V.mesh.device, self.V.bs
+        st = m.structured
+        L.degree, L.n = 1, (None if refined else n)
+        if refined:
+            # n is the level's mesh: the same one below a degree-2 level, else the parent. Either
+            # way the fine nodes are the coarse mesh's vertices, then one per edge of it
+            cm = n
+            F.transfer = EdgeTransfer(fmesh.entities(cm, 1)[0], cm.num_vertices, bs)
+            if F.transfer.num_fine_dofs != F.V.num_dofs:
+                raise ValueError("the mesh's parent does not have the numbering of mesh.refine")
+            F.inject = slice(0, cm.num_vertices)
+            F.parents = None if cm is F.V.mesh else \
+                torch.arange(F.V.mesh.num_cells, device=dev, dtype=torch.int64) >> m.tdim
+            L.marker = None if F.marker is None else F.marker[:F.transfer.num_coarse_dofs].contiguous()
+        else:
+            if n == F.n:
+                cm = F.V.mesh
+            elif m.tdim == 2:
+                cm = fmesh.create_rectangle(st["lengths"], n, m.cell_type, st.get("diagonal", "right"), dev)
             else:
-                F = self._levels[-1]
-                if refined:
-                    # n is the level's mesh: the same one below a degree-2 level, else the parent. Either
-                    # way the fine nodes are the coarse mesh's vertices, then one per edge of it
-                    cm = n
-                    F.transfer = EdgeTransfer(fmesh.entities(cm, 1)[0], cm.num_vertices, bs)
-                    if F.transfer.num_fine_dofs != F.V.num_dofs:
-                        raise ValueError("the mesh's parent does not have the numbering of mesh.refine")
-                    F.inject = slice(0, cm.num_vertices)
-                    F.parents = None if cm is F.V.mesh else \
-                        torch.arange(F.V.mesh.num_cells, device=dev, dtype=torch.int64) >> m.tdim
-                    L.marker = None if F.marker is None else F.marker[:F.transfer.num_coarse_dofs].contiguous()
-                else:
-                    if n == F.n:
-                        cm = F.V.mesh
-                    elif m.tdim == 2:
-                        cm = fmesh.create_rectangle(st["lengths"], n, m.cell_type, st.get("diagonal", "right"), dev)
-                    else:
-                        cm = fmesh.create_box(st["lengths"], n, m.cell_type, dev)
-                    F.transfer = Transfer(m.tdim, simplex, bs, n)
-                    F.inject = injection_nodes(F.transfer, dev)
-                    F.parents = None if n == F.n else parent_cells(m.cell_type, n, dev)
-                    L.marker = coarsen_marker(F.marker, F.transfer)
-                L.V = fem.functionspace(cm, ("Lagrange", 1, (bs,)))
-                self._coarse_form(F, L)
-                L.A = fem.create_matrix(L.a)
-                L.kind = "assembled"
-            L.transfer = None
-            nd = L.V.num_dofs
-            L.r, L.z, L.d, L.t = (torch.zeros(nd, dtype=torch.float64, device=dev) for _ in range(4))
-            L.Dinv = L.coef = L.Ainv = None
-            self._levels.append(L)
+                cm = fmesh.create_box(st["lengths"], n, m.cell_type, dev)
+            F.transfer = Transfer(m.tdim, fem.is_simplex(m.cell_type), bs, n)
+            F.inject = injection_nodes(F.transfer, dev)
+            F.parents = None if n == F.n else parent_cells(m.cell_type, n, dev)
+            L.marker = coarsen_marker(F.marker, F.transfer)
+        L.V = fem.functionspace(cm, ("Lagrange", 1, (bs,)))
+        self._coarse_form(F, L)
+        L.A = fem.create_matrix(L.a)
+        L.kind = "assembled"
+        return self._add_level(L, bs, L.V.num_dofs)
+
+    def _add_level(self, L, bs: int, ndofs: int):
+        L.bs, L.ndofs = int(bs), int(ndofs)
+        L.transfer = None
+        dev = self.V.mesh.device
+        L.r, L.z, L.d, L.t = (torch.zeros(L.ndofs, dtype=torch.float64, device=dev) for _ in range(4))
+        L.Dinv = L.coef = L.Ainv = None
+        self._levels.append(L)
+        return L
+
+    def _close_hierarchy(self):
+        """The last level is inverted densely if it is small enough, else it gets the fixed polynomial."""
         last = self._levels[-1]
-        last.direct = last.V.num_dofs <= self.coarse_dofs
+        last.direct = last.ndofs <= self.coarse_dofs
         if len(self._levels) > 1 or last.direct:
             last.kind = "direct" if last.direct else "chebyshev"
         mk = self._levels[0].marker
         self._free = None if mk is None else (mk == 0).to(torch.float64)
         # z = r / diagonal on the constrained dofs, + 0 (r / inf) on the free ones
         self._cdiv = None if mk is None else torch.where(mk != 0, self.diagonal, float("inf")).to(torch.float64)
-        self._gen = torch.Generator(device=dev)
-        self._nnz0 = None
 
     # ------------------------------------------------------------------------------ hierarchy
     def _coarse_form(self, F, L):
@@ -504,7 +502,7 @@ class GeometricMultigrid:
 
     @property
     def levels(self) -> list:
-        return [(L.degree, L.n, L.V.num_dofs, L.kind) for L in self._levels]
+        return [(L.degree, L.n, L.ndofs, L.kind) for L in self._levels]
 
     @property
     def operator_complexity(self) -> float:
@@ -520,7 +518,7 @@ class GeometricMultigrid:
     def _estimate_lmax(self, L) -> float:
         """Largest eigenvalue of D^-1 A from EIG_STEPS steps of block-Jacobi CG on a seeded right-hand
         side (the Lanczos tridiagonal of the CG coefficients); deterministic."""
-        bs = L.V.bs
+        bs = L.bs
         r, z, p, Ap = L.r, L.z, L.d, L.t
         self._gen.manual_seed(1234)
         r.uniform_(-1.0, 1.0, generator=self._gen)
@@ -557,31 +555,24 @@ class GeometricMultigrid:
             v.zero_()
         return float(np.linalg.eigvalsh(T)[-1])
 
-    def update(self):
-        """Re-inject the state, re-assemble the coarse matrices and refresh each level's block-Jacobi
-        inverse, eigenvalue estimate and the coarsest level's dense inverse."""
-        Ls = self._levels
-        for F, L in zip(Ls[:-1], Ls[1:]):
-            self._refill(F, L)
-            fem.assemble_matrix(L.a, bcs=L.bcs, diagonal=self.diagonal, A=L.A)
-        for L in Ls:
-            last = L is Ls[-1]
-            if last and L.direct:
-                L.Ainv = self._dense_inverse(L)
-                continue
-            D = L.A.block_diagonal()
-            bad = D.abs().sum((1, 2)) == 0  # rows without a diagonal block keep identity (as KrylovSolver)
-            D[bad] = torch.eye(L.V.bs, dtype=D.dtype, device=D.device)
-            L.Dinv = torch.linalg.inv(D).contiguous()
-            L.lmax = self._estimate_lmax(L)
-            degree = COARSE_CHEB_DEGREE if last else self.smoother_degree
-            L.coef = chebyshev_coefficients(CHEB_LOWER * L.lmax, CHEB_UPPER * L.lmax, degree)
-        self.updates += 1
+    def _setup_level(self, L, last: bool):
+        """The level's block-Jacobi inverse, eigenvalue estimate and polynomial, or, on a last level small
+        enough, its dense inverse."""
+        if last and L.direct:
+            L.Ainv = self._dense_inverse(L)
+            return
+        D = L.A.block_diagonal()
+        bad = D.abs().sum((1, 2)) == 0  # rows without a diagonal block keep identity (as KrylovSolver)
+        D[bad] = torch.eye(L.bs, dtype=D.dtype, device=D.device)
+        L.Dinv = torch.linalg.inv(D).contiguous()
+        L.lmax = self._estimate_lmax(L)
+        degree = COARSE_CHEB_DEGREE if last else self.smoother_degree
+        L.coef = chebyshev_coefficients(CHEB_LOWER * L.lmax, CHEB_UPPER * L.lmax, degree)
 
     def _dense_inverse(self, L) -> torch.Tensor:
         A = L.A
         if not hasattr(A, "indptr"):  # a single matrix-free level: probe it with the identity
-            n = L.V.num_dofs
+            n = L.ndofs
             eye = torch.eye(n, dtype=torch.float64, device=L.r.device)
             M = torch.stack([A.mult(eye[j].contiguous()) for j in range(n)], 1)
         else:
@@ -605,6 +596,14 @@ class GeometricMultigrid:
                 Ax = L.A.mult(L.z, L.t)
             cheb_step(L.Dinv, L.r, Ax, cd, cr, L.d, L.z)
 
+    def _restrict(self, L, C):
+        """C.r = the restriction of the residual in L.t."""
+        restrict(L.transfer, L.t, C.r, bc_f=L.marker, bc_c=C.marker)
+
+    def _prolong(self, L, C):
+        """L.z += the prolongation of the coarse correction C.z."""
+        prolong(L.transfer, C.z, L.z, bc_c=C.marker, bc_f=L.marker, add=True)
+
     def _cycle(self, li: int):
         L = self._levels[li]
         if li == len(self._levels) - 1:
@@ -617,9 +616,9 @@ class GeometricMultigrid:
         self._smooth(L, True)
         L.A.mult(L.z, L.t)
         torch.sub(L.r, L.t, out=L.t)
-        restrict(L.transfer, L.t, C.r, bc_f=L.marker, bc_c=C.marker)
+        self._restrict(L, C)
         self._cycle(li + 1)
-        prolong(L.transfer, C.z, L.z, bc_c=C.marker, bc_f=L.marker, add=True)
+        self._prolong(L, C)
         self._smooth(L, False)
 
     def apply(self, r: torch.Tensor, z: torch.Tensor | None = None) -> torch.Tensor:
@@ -641,3 +640,215 @@ class GeometricMultigrid:
         else:
             torch.addcdiv(L0.z, r, self._cdiv, out=z)
         return z
+
+
+class GeometricMultigrid(_VCycle):
+    """One V-cycle of geometric multigrid as a fixed, symmetric positive definite preconditioner
+    (``apply(r, z)`` / ``update()``: the interface of ``nls.KrylovSolver.set_preconditioner``).
+
+    a: the Jacobian form on a structured mesh (LinearElasticity / AsymDamage / NeoHookean); bcs, diagonal
+    as ``fem.assemble_matrix``. Level 0 is the form's own space with ``fine_operator`` (anything with
+    ``mult(x, y)`` and ``block_diagonal()``) or ``fem.JacobianOperator(a, bcs, diagonal)``; a degree-2
+    space is followed by degree 1 on the same mesh; further levels halve every ``n`` (``plan_hierarchy``).
+    Coarse forms are rediscretised with the same form class: per-cell coefficients are the mean over the
+    child cells, the nodal state is injected, a coarse node is constrained where its coinciding fine node
+    is; coarse operators are assembled (``fem.assemble_matrix``). The smoother is Chebyshev of degree
+    ``smoother_degree`` over block-Jacobi on [0.1, 1.1] x the estimated largest eigenvalue of D^-1 A,
+    the same polynomial before and after the coarse correction. A coarsest level of at most
+    ``coarse_dofs`` dofs is inverted densely at ``update()``, a larger one gets a fixed Chebyshev
+    polynomial of degree 8.
+
+    On a mesh without a lattice (``mesh.structured is None``: triangles and tetrahedra) the levels follow
+    ``plan_refined_hierarchy``: degree 2 to degree 1 on the same mesh, then degree 1 on every
+    ``mesh.parent`` that ``mesh.refine`` left behind. The transfer is an ``EdgeTransfer``, injection takes
+    the first ``ncoarse`` nodes, the coarse marker is the leading slice of the fine one, the parent of cell
+    ``j`` is ``j >> tdim``; ``levels`` reports ``n = None``.
+
+    ``update()`` must follow every change of the state (``KrylovSolver.set_operator`` calls it); the
+    first ``apply`` runs it if nobody has. ``levels``: [(degree, n, num_dofs, kind)];
+    ``operator_complexity``: stored matrix entries of all levels over those of the level-0 matrix."""
+
+    def __init__(self, a, bcs=None, diagonal: float = 1.0, fine_operator=None, smoother_degree: int = 2,
+                 coarse_dofs: int = 6000, max_levels: int | None = None):
+        self._init_common(a, bcs, diagonal, smoother_degree, coarse_dofs)
+        V = a.V
+        refined = V.mesh.structured is None
+        table = (plan_refined_hierarchy if refined else plan_hierarchy)(V, coarse_dofs, max_levels)
+        if V.bs != V.mesh.gdim:
+            raise ValueError("the form's space must be a vector Lagrange space (bs = gdim)")
+        for li, (p, n) in enumerate(table):
+            if li == 0:
+                L = self._fine_level(fine_operator)
+                L.n = None if refined else n
+            else:
+                self._geometric_level(self._levels[-1], n, refined)
+        self._close_hierarchy()
+
+    def update(self):
+        """Re-inject the state, re-assemble the coarse matrices and refresh each level's block-Jacobi
+        inverse, eigenvalue estimate and the coarsest level's dense inverse."""
+        Ls = self._levels
+        for F, L in zip(Ls[:-1], Ls[1:]):
+            self._refill(F, L)
+            fem.assemble_matrix(L.a, bcs=L.bcs, diagonal=self.diagonal, A=L.A)
+        for L in Ls:
+            self._setup_level(L, L is Ls[-1])
+        self.updates += 1
+
+
+class SmoothedAggregation(_VCycle):
+    """One V-cycle of smoothed-aggregation algebraic multigrid as a fixed, symmetric positive definite
+    preconditioner: ``GeometricMultigrid``'s contract (``apply(r, z)`` / ``update()``, ``levels``,
+    ``operator_complexity``, usable in ``nls.KrylovSolver.set_preconditioner``) on meshes that have neither a
+    lattice nor a chain of ``mesh.parent``. The coarse levels come from the matrix and the node coordinates
+    alone, with the rigid-body modes as the near-null space (``femasm.amg``).
+
+    a: the Jacobian form on a vector Lagrange space with ``bs == gdim`` in 2-D or 3-D: degree 1 with any cell
+    type on any mesh, or degree 2 where ``GeometricMultigrid`` has a P2 -> P1 step (simplices anywhere,
+    lattice meshes); everything else (scalar spaces, DG, degree 3, ``z_range`` slabs) raises ValueError.
+    Level 0 is the form's space with ``fine_operator`` or a matrix-free ``fem.JacobianOperator``; a degree-2
+    level is followed by the rediscretised, assembled degree-1 level on the same mesh, exactly as in
+    ``GeometricMultigrid``; below the degree-1 level every level is algebraic: 3 (2-D) or 6 (3-D) dofs per
+    aggregate, ``A_c = P^T A P`` with ``P = M_f (T - omega D^-1 A T)``.
+
+    The algebraic set-up reads the degree-1 level's matrix entries: the level's own assembled matrix below
+    degree 2; at degree 1 a ``la.MatrixCSR`` given as ``fine_operator`` (what ``problem.matrix()`` is in
+    assembled mode); at degree 1 otherwise a matrix this class assembles at every ``update()`` and keeps
+    resident, while the given or matrix-free operator still does the level-0 smoothing.
+
+    ``update(rebuild=False)`` redoes the numeric Galerkin products, the block-Jacobi inverses, the eigenvalue
+    estimates and the dense inverse of the coarsest level. Aggregates, sparsity patterns, product lists and
+    the prolongators' values are built once, at the first ``update()``, from the matrix of that moment;
+    ``update(rebuild=True)`` smooths the prolongators again with the current matrices. ``updates`` and
+    ``rebuilds`` count the two kinds of call (the first ``update()`` is both). Levels stop at ``coarse_dofs``
+    dofs (dense inverse) or at ``max_levels`` (fixed Chebyshev polynomial), as in ``GeometricMultigrid``.
+
+    ``levels``: [(degree, None, num_dofs, kind)], degree 0 and kind "galerkin" on the algebraic levels; it and
+    ``operator_complexity`` run the first ``update()`` if nobody has, since the hierarchy is not known before."""
+
+    def __init__(self, a, bcs=None, diagonal: float = 1.0, fine_operator=None, smoother_degree: int = 2,
+                 coarse_dofs: int = 6000, max_levels: int | None = None):
+        from .la import MatrixCSR
+
+        self._init_common(a, bcs, diagonal, smoother_degree, coarse_dofs)
+        V = a.V
+        m = V.mesh
+        st = m.structured
+        if V.family in ("DG", "Discontinuous Lagrange") or V.degree not in (1, 2):
+            raise ValueError(f"SmoothedAggregation serves Lagrange degree 1 and 2, not {V.family} degree {V.degree}")
+        if V.bs != m.gdim or m.gdim not in (2, 3):
+            raise ValueError("the form's space must be a vector Lagrange space (bs = gdim) in 2-D or 3-D: the "
+                             "rigid-body modes are the near-null space")
+        if st is not None and st.get("z_range") is not None and tuple(st["z_range"]) != (0, int(st["n"][-1])):
+            raise ValueError(f"SmoothedAggregation needs the whole box, not the z_range={tuple(st['z_range'])} slab")
+        if V.degree == 2:
+            if st is None and not fem.is_simplex(m.cell_type):
+                raise ValueError(f"SmoothedAggregation at degree 2 on an unstructured mesh needs triangles or "
+                                 f"tetrahedra, not {CellType(m.cell_type).name} cells (the P2 -> P1 edge transfer)")
+            if st is not None and m.cell_type == CellType.triangle and st.get("diagonal", "right") != "right":
+                raise ValueError("SmoothedAggregation at degree 2 needs diagonal='right' triangles (the lattice "
+                                 "P2 -> P1 transfer)")
+        if max_levels is not None and max_levels < 1:
+            raise ValueError("max_levels must be at least 1")
+        self.max_levels = max_levels
+        self.rebuilds = 0
+        more = lambda: (max_levels is None or len(self._levels) < max_levels) and \
+            self._levels[-1].ndofs > self.coarse_dofs
+        L = self._fine_level(fine_operator)
+        if V.degree == 2 and more():
+            if st is not None:
+                L.n = tuple(int(k) for k in st["n"])  # (the lattice transfer on the same n)
+            L = self._geometric_level(L, L.n if st is not None else m, st is None)
+            self._levels[0].n = L.n = None
+        # the degree-1 level, whose matrix entries the algebraic set-up reads
+        self._p1 = L if L.degree == 1 else None
+        self._A1 = None
+        if self._p1 is not None:
+            self._p1.x = self._p1.V.tabulate_dof_coordinates()
+            # (a matrix of this class's own, where the level's operator is none, is created by the first update())
+            self._p1.entries = self._p1.A if isinstance(self._p1.A, MatrixCSR) else None
+        self._more = more
+        self._built = False  # the algebraic levels are added, and the hierarchy closed, by the first update()
+
+    @property
+    def levels(self) -> list:
+        if not self._built:
+            self.update()
+        return super().levels
+
+    @property
+    def operator_complexity(self) -> float:
+        if not self._built:
+            self.update()
+        return _VCycle.operator_complexity.fget(self)
+
+    @property
+    def transfers(self) -> list:
+        """The ``amg.Aggregation`` of every algebraic transfer, finest first."""
+        return [L.transfer for L in self._levels if isinstance(L.transfer, amg.Aggregation)]
+
+    def _restrict(self, L, C):
+        if isinstance(L.transfer, amg.Aggregation):
+            L.transfer.Pt.mult(L.t, C.r)
+        else:
+            super()._restrict(L, C)
+
+    def _prolong(self, L, C):
+        if isinstance(L.transfer, amg.Aggregation):
+            L.transfer.P.mult(C.z, L.z, add=True)
+        else:
+            super()._prolong(L, C)
+
+    def _coarsen(self, L):
+        """Aggregate level L and append the level below it; False when there is nothing to gain."""
+        tr = amg.Aggregation(L.entries, L.x, L.marker)
+        nr = tr.nr
+        if tr.nagg == 0 or tr.nagg * nr >= L.ndofs:
+            return False
+        C = _Level()
+        C.degree, C.n, C.kind = 0, None, "galerkin"
+        C.A = C.entries = tr.Ac
+        C.x, C.marker = tr.xc, tr.marker_c
+        L.transfer = tr
+        self._add_level(C, nr, tr.nagg * nr)
+        return True
+
+    def update(self, rebuild: bool = False):
+        """Redo everything that depends on the matrix entries; with ``rebuild`` (and at the first call) also
+        the prolongators' values. See the class."""
+        Ls = self._levels
+        first = not self._built
+        p1 = self._p1
+        if p1 is None:  # a degree-2 space small enough to invert, or max_levels = 1
+            if first:
+                self._close_hierarchy()
+            self._setup_level(Ls[0], True)
+        else:
+            i1 = Ls.index(p1)
+            if i1 == 1:
+                self._refill(Ls[0], p1)
+                fem.assemble_matrix(p1.a, bcs=p1.bcs, diagonal=self.diagonal, A=p1.A)
+                self._setup_level(Ls[0], False)
+            elif p1.entries is None or self._A1 is not None:
+                if self._A1 is None:
+                    p1.entries = self._A1 = fem.create_matrix(self.a)
+                fem.assemble_matrix(self.a, bcs=self.bcs, diagonal=self.diagonal, A=self._A1)
+            li = i1
+            while True:
+                L = Ls[li]
+                if first and li == len(Ls) - 1 and self._more():
+                    self._coarsen(L)
+                last = li == len(Ls) - 1
+                if last and first:
+                    self._close_hierarchy()
+                self._setup_level(L, last)
+                if last:
+                    break
+                if first or rebuild:
+                    L.transfer.smooth(L.entries, L.Dinv, L.lmax)
+                L.transfer.galerkin(L.entries)
+                li += 1
+        self._built = True
+        self.updates += 1
+        if first or rebuild:
+            self.rebuilds += 1

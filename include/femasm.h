@@ -687,6 +687,43 @@ int fa_eval_points(const fa_mesh* mesh /* its cells/degree/nn are the space's do
                    int32_t bs /*1..3*/, int64_t npts, const int32_t* cell, const double* X,
                    double* val /*[npts][bs] or NULL*/, double* grad /*[npts][bs][gdim] or NULL*/, void* stream);
 
+/* ---- smoothed-aggregation algebraic multigrid (femasm_amg.hip, fa_version() >= 109) ----
+ * The reference preconditions with BoomerAMG on a mesh nobody refined; femasm.mg.SmoothedAggregation builds
+ * its coarse levels from the matrix and the node coordinates alone (rigid-body modes as the near-null
+ * space). Aggregates, sparsity patterns and product lists are set-up work of the caller (femasm: torch
+ * ops on the device, once); these calls are what runs at every Newton step and inside the V-cycle. None
+ * of them allocates or synchronises, all index arithmetic is 64-bit, all sums run in a fixed order with
+ * no atomics (bit-identical run to run), and an index outside its operand is skipped, never dereferenced.
+ *
+ * fa_bcsr_mult: y (+)= B x for a block-CSR matrix of nrows x ncols blocks, each [br][bc] row-major:
+ * indptr [nrows + 1], indices [nblocks] block columns, data [nblocks][br][bc]; x [ncols * bc], y
+ * [nrows * br]; add = 0 overwrites y. Block shapes (2,3), (3,2), (3,3), (3,6), (6,3), (6,6): a
+ * prolongator, its stored transpose (the restriction as a gather: the exact transpose) and the coarse
+ * matrices with 6-dof nodes; anything else is FA_E_UNSUPPORTED. Eight lanes share a block row. */
+int fa_bcsr_mult(int64_t nrows, int64_t ncols, int32_t br, int32_t bc, const int64_t* indptr, const int32_t* indices,
+                 const double* data, const double* x, int32_t add, double* y, void* stream);
+
+/* fa_bcsr_product: the numeric phase of a block SpGEMM on a precomputed inverted list,
+ *   out[s] = sum over q in [optr[s], optr[s + 1]) of X[xa[q]] * Y[yb[q]],   s < nout,
+ * X blocks [r][k], Y blocks [k][c], out blocks [r][c], all row-major; xa / yb are block slots of X (< nx)
+ * and Y (< ny), nprod the length of the lists. An empty range gives a zero block. Shapes (r, k, c):
+ * (2,2,3), (3,3,3), (3,3,6), (6,6,6) (A*T, A*P) and (3,2,3), (6,3,6) (P^T*Y); anything else is
+ * FA_E_UNSUPPORTED. A group of lanes per output block, lane = (row of the block, stride offset into the
+ * list): a wave when nprod > 8 nout, a quarter wave otherwise; partial sums meet in a fixed tree. */
+int fa_bcsr_product(int64_t nout, int32_t r, int32_t k, int32_t c, const int64_t* optr, int64_t nprod,
+                    const int32_t* xa, const int32_t* yb, const double* X, int64_t nx, const double* Y, int64_t ny,
+                    double* out, void* stream);
+
+/* The contract of fa_cheb_step at bs = 6 (fa_cheb_step itself serves bs 1 to 3). */
+int fa_cheb_step6(int64_t nnodes, const double* Dinv, const double* b, const double* Ax /* or NULL */, double c_d,
+                  double c_r, double* d, double* x, void* stream);
+
+/* out[i] = free_nodes[i] ? max over k in row i of in[indices[k]] : 0 (free_nodes NULL: every row is free; an
+ * empty row gives 0); in [nin], out [nrows], int64. The graph primitive of the deterministic MIS(2)
+ * aggregation; the few rounds are driven by the caller. */
+int fa_csr_row_max(int64_t nrows, const int64_t* indptr, const int32_t* indices, const int8_t* free_nodes /* or NULL */,
+                   const int64_t* in, int64_t nin, int64_t* out, void* stream);
+
 /* Measurement helper (not part of the reference interface): a 16-B-per-lane grid-stride stream
  * over n doubles (n even, 16-B aligned buffers) for the measured HBM peak beside the 8 TB/s spec
  * (SURVEY.md section 8(d)). mode 0: dst = src (copy), 1: dst = 1.0 (write only), 2: read src

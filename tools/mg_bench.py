@@ -19,12 +19,22 @@
                     refined R times (or, with --box, the N^3 tetrahedron box without its lattice record),
                     Lagrange --degree, E per physical tag, same bcs.
 
+  --amg             solve mode with mg.SmoothedAggregation: the mesh of the solve mode (lattice box, or with
+                    --refine the refined square.msh / box) is rebuilt without its lattice record and without
+                    its parents, so the package can only coarsen it algebraically. Reports levels, operator
+                    complexity, set-up (the first update()), update() and per-apply times, the product-list
+                    lengths of every algebraic transfer, and PCG iterations and solve time against
+                    block-Jacobi; and, on the original mesh with its chain or lattice, against
+                    mg.GeometricMultigrid.
+
 Prints one JSON line.
 
   python tools/mg_bench.py --mode transfer --n 96 [--out profiles/multigrid/transfer_n96.json]
   python tools/mg_bench.py --mode solve --n 48 --rtol 1e-8 [--out profiles/multigrid/solve_n48.json]
   python tools/mg_bench.py --mode transfer --n 48 --refine 1 [--out profiles/multigrid/edge_transfer_n48_r1.json]
   python tools/mg_bench.py --mode solve --refine 3 --degree 1 --rtol 1e-10
+  python tools/mg_bench.py --mode solve --amg --refine 6 --degree 1 [--out profiles/amg/square_r6_p1.json]
+  python tools/mg_bench.py --mode solve --amg --n 32 [--out profiles/amg/box32_p2.json]
 
 Fails when no GPU is found: a CPU run has no timing to give.
 """
@@ -138,6 +148,89 @@ def edge_transfer_mode(args, dev) -> dict:
     return res
 
 
+def _krylov_run(args, A, b, M):
+    """(result record, solution) of one PCG solve with preconditioner M (None: block-Jacobi)."""
+    ks = nls.KrylovSolver(rtol=args.rtol, max_it=args.max_it)
+    if M is not None:
+        ks.set_preconditioner(M)
+    x = torch.zeros_like(b)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    ks.set_operator(A)
+    torch.cuda.synchronize()
+    t1 = time.perf_counter()
+    ks.solve(x, b)  # untimed: the first use of a kernel or a BLAS routine loads it
+    torch.cuda.synchronize()
+    t1w = time.perf_counter()
+    its = ks.solve(x, b)
+    torch.cuda.synchronize()
+    t2 = time.perf_counter()
+    r = b - A.mult(x)
+    rec = {"iterations": its, "first_solve_s": t1w - t1, "setup_s": t1 - t0, "solve_s": t2 - t1w, "true_residual_rel": float(r.norm() / b.norm())}
+    if M is not None:
+        z = torch.empty_like(b)
+        rec.update(levels=M.levels, operator_complexity=M.operator_complexity,
+                   vcycle_ms=timed(lambda: M.apply(b, z), args.steps, args.warmup))
+    return rec, x
+
+
+def _linear_problem(args, m, dev):
+    V = fem.functionspace(m, ("Lagrange", args.degree if args.refine else 2, (m.gdim,)))
+    cid = m.cell_tags.to(torch.int64) if m.cell_tags is not None else \
+        torch.arange(m.num_cells, device=dev, dtype=torch.int64)
+    E = torch.tensor(e_range(), dtype=torch.float64, device=dev)[cid % 200]
+    u = fem.Function(V)
+    a = fem.LinearElasticity(V, E=E, nu=0.3, u=u)
+    left = fem.locate_dofs_geometrical(V, lambda x: torch.isclose(x[0], torch.zeros_like(x[0])))
+    right = fem.locate_dofs_geometrical(V, lambda x: torch.isclose(x[0], torch.ones_like(x[0])))
+    bcs = [fem.dirichletbc(0.0, left, V), fem.dirichletbc([0.01] + [0.0] * (m.gdim - 1), right, V)]
+    problem = nls.NonlinearProblem(a, u, bcs, matrix_free=True)
+    b = torch.zeros(V.num_dofs, dtype=torch.float64, device=dev)
+    problem.F(u.x, b)
+    return V, a, bcs, problem.matrix(), b
+
+
+def amg_mode(args, dev) -> dict:
+    n = args.n
+    if args.refine:
+        full = unstructured_box(n, dev) if args.box else \
+            mesh.read_gmsh(os.path.join(ROOT, "tests", "golden", "square.msh"), gdim=2, device=dev)
+        for _ in range(args.refine):
+            full = mesh.refine(full)
+    else:
+        full = mesh.create_box((1.0, 1.0, 1.0), (n, n, n), mesh.CellType.tetrahedron, device=dev)
+    m = mesh.Mesh(full.cell_type, full.x, full.cells, full.cell_tags, None)  # no lattice, no parents
+    V, a, bcs, A, b = _linear_problem(args, m, dev)
+    res = {"cells": m.num_cells, "dofs": V.num_dofs, "degree": V.degree, "rtol": args.rtol}
+    res["jacobi"], xj = _krylov_run(args, A, b, None)
+    M = mg.SmoothedAggregation(a, bcs, fine_operator=A, smoother_degree=args.smoother_degree,
+                               coarse_dofs=args.coarse_dofs)
+    res["amg"], xa = _krylov_run(args, A, b, M)  # setup_s: the first update() (aggregates, lists, prolongators)
+    upd = []
+    for _ in range(3):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        M.update()
+        torch.cuda.synchronize()
+        upd.append(time.perf_counter() - t0)
+    res["amg"].update(update_s=sorted(upd)[1], rebuilds=M.rebuilds, updates=M.updates,
+                      lmax=[getattr(L, "lmax", None) for L in M._levels])
+    res["amg"]["transfers"] = [
+        {"fine_nodes": tr.n, "aggregates": tr.nagg, "dead": int(tr.dead.sum()), "list_bytes": tr.list_bytes(),
+         "lists": {k: dict(zip(("products", "blocks", "median", "max"), (p.nprod, p.nout) + p.list_stats()))
+                   for k, p in (("A.T", tr.AT), ("A.P", tr.AP), ("Pt.Y", tr.PtY))}} for tr in M.transfers]
+    res["amg"]["solutions_rel_diff"] = float((xa - xj).norm() / xj.norm())
+    if full.structured is not None or full.parent is not None:
+        Vg, ag, bcg, Ag, bg = _linear_problem(args, full, dev)
+        G = mg.GeometricMultigrid(ag, bcg, fine_operator=Ag, smoother_degree=args.smoother_degree,
+                                  coarse_dofs=args.coarse_dofs)
+        res["gmg"], xg = _krylov_run(args, Ag, bg, G)
+        # (a lattice mesh numbers its degree-2 nodes differently: compare the norms there)
+        res["gmg"]["solutions_rel_diff"] = float((xg - xj).norm() / xj.norm()) if full.structured is None else \
+            abs(float(xg.norm() / xj.norm()) - 1.0)
+    return res
+
+
 def solve_mode(args, dev) -> dict:
     n = args.n
     if args.refine:
@@ -207,6 +300,7 @@ def main():
     ap.add_argument("--refine", type=int, default=0, help="refine an unstructured mesh this many times")
     ap.add_argument("--box", action="store_true", help="solve --refine: the N^3 tetrahedron box, not square.msh")
     ap.add_argument("--degree", type=int, default=2, help="solve --refine: Lagrange degree")
+    ap.add_argument("--amg", action="store_true", help="solve: smoothed aggregation on the mesh without lattice or parents")
     ap.add_argument("--coarse-dofs", type=int, default=6000)
     ap.add_argument("--rtol", type=float, default=1e-8)
     ap.add_argument("--max-it", type=int, default=20000)
@@ -223,7 +317,7 @@ def main():
     if args.refine < 0:
         sys.exit("mg_bench: --refine must not be negative")
     if args.mode == "solve":
-        res.update(solve_mode(args, dev))
+        res.update(amg_mode(args, dev) if args.amg else solve_mode(args, dev))
     else:
         res.update(edge_transfer_mode(args, dev) if args.refine else transfer_mode(args, dev))
     line = json.dumps(res)
