@@ -34,6 +34,7 @@
 
 #include "../../include/femasm.h"
 #include "elements.h"
+#include "plan_order.h"
 
 using namespace femasm;
 
@@ -4322,19 +4323,20 @@ extern "C" int fa_plan_slots(const fa_mesh* mesh, const fa_adjacency* adj, const
 // the wave on its own, and two lanes of a quarter conflict when their slots are equal mod 16
 // (72-B blocks); k lanes on one residue cost k passes, lanes on one slot a little more. Within each
 // quarter of the kernel's item -> lane mapping the order in which every lane visits its NBG column
-// slots is chosen to minimise sum over steps of the largest residue count (the passes), with the
-// sum of squared counts as tie-break: identity start, then pairwise step swaps per lane until no
-// swap improves. The slot map then holds (b << 10) | position in that order. One thread per
+// slots is chosen to minimise sum over steps of the largest residue count (the passes), as an edge
+// colouring of the quarter's lanes x residues graph with NBG colours (plan_order.h,
+// plan_order::order_quarter): the equitable colouring where no residue holds more
+// than NBG blocks (NBG passes, the optimum); elsewhere the earlier order (identity start, pairwise
+// step swaps per lane until none improves) and then Kempe swaps that bring the over-full residues'
+// extra steps together. The slot map then holds (b << 10) | position in that order. One thread per
 // (chunk, quarter).
 // Positional plans (eperm != NULL): position jj of a chunk holds entry eperm[a0 + jj]; the plain
 // map is read from src and written by position, with chunk-relative block positions.
-// alternating-path moves of the slot order search (k_order_slots): rounds (with FA_PLAN_ORDER_SEARCH)
-// and lanes per chain. Opt-in since round 5: on config E they took the plan from 1.7 to 20 s for
-// 37.6 -> 37.4 ms per assembly (break-even after ~90,000 assemblies; the reference assembles J a few
-// times per Newton solve)
+// rounds of the earlier order's alternating-path chain search (plan_order::search_chains), run with
+// FA_PLAN_ORDER_SEARCH only, which also aligns from a second start (the equitable colouring) and keeps
+// the better order: config E's plan 1.1 -> 4.8 s for 2 % fewer passes.
 constexpr int kKempeRounds = 4;
-constexpr int kKempeLen = 6;
-// The search's per-thread state (residues, picks, counts, step maxima) sits in LDS, one slice per
+// A quarter's state (residues, picks, counts, step maxima) sits in LDS, one plan_order::Quarter per
 // thread of a 64-thread workgroup (round 5; in scratch it made the search with the alternating-path
 // moves a 19.6-s launch on config E).
 constexpr int kOrderThreads = 64;
@@ -4345,14 +4347,9 @@ __global__ __launch_bounds__(kOrderThreads) void k_order_slots(const int64_t* __
                                                                 int groups_per_chunk, uint16_t* __restrict__ slots,
                                                                 const uint16_t* __restrict__ src,
                                                                 const uint16_t* __restrict__ eperm, int rounds) {
-  constexpr int NBG = NN / NSPLIT, Q = 16;
-  __shared__ uint8_t s_res[kOrderThreads][Q][NBG], s_pick[kOrderThreads][Q][NBG], s_cnt[kOrderThreads][NBG][16];
-  __shared__ int s_mx[kOrderThreads][NBG], s_nmx[kOrderThreads][NBG];
-  auto& res = s_res[threadIdx.x];
-  auto& pick = s_pick[threadIdx.x];
-  auto& cnt = s_cnt[threadIdx.x];
-  auto& mx = s_mx[threadIdx.x];
-  auto& nmx = s_nmx[threadIdx.x];
+  constexpr int NBG = NN / NSPLIT, Q = plan_order::kLanes;
+  __shared__ plan_order::Quarter<NBG> s_quarter[kOrderThreads];
+  plan_order::Quarter<NBG>& S = s_quarter[threadIdx.x];
   const int64_t total = nchunks * groups_per_chunk;
   for (int64_t gid = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; gid < total;
        gid += (int64_t)gridDim.x * blockDim.x) {
@@ -4372,8 +4369,6 @@ __global__ __launch_bounds__(kOrderThreads) void k_order_slots(const int64_t* __
     int64_t ent[Q];
     int base[Q];
     const uint16_t* rd = eperm ? src : slots;
-    for (int t = 0; t < NBG; ++t)
-      for (int r = 0; r < 16; ++r) cnt[t][r] = 0;
     for (int q = 0; q < nl; ++q) {
       const int p = p0 + q;
       const int part = p % NSPLIT;
@@ -4390,114 +4385,17 @@ __global__ __launch_bounds__(kOrderThreads) void k_order_slots(const int64_t* __
       ent[q] = (eperm ? a0 + p / NSPLIT : e) * NN + part * NBG;
       for (int t = 0; t < NBG; ++t) {
         off[q][t] = rd[ein + t];
-        res[q][t] = (uint8_t)((rowlo + off[q][t]) & 15);
-        pick[q][t] = (uint8_t)t;
-        ++cnt[t][res[q][t]];
+        S.st[q][t] = (uint8_t)(((rowlo + off[q][t]) & 15) | (t << 4));
       }
     }
-    // step maxima and how many residues reach them: a swap is then priced in O(1) and the two
-    // steps are recounted only when it is taken
-    auto recount = [&](int t) {
-      int m = 0, n = 0;
-      for (int r = 0; r < 16; ++r) {
-        const int v = cnt[t][r];
-        if (v > m) { m = v; n = 1; } else if (v == m) ++n;
-      }
-      mx[t] = m;
-      nmx[t] = n;
-    };
-    // new maximum of step t after one add moves from residue ro (count co) to rn (count cn)
-    auto moved_max = [&](int t, int co, int cn) {
-      if (cn + 1 > mx[t]) return cn + 1;
-      if (co == mx[t] && nmx[t] == 1 && cn + 1 < mx[t]) return mx[t] - 1;
-      return mx[t];
-    };
-    for (int t = 0; t < NBG; ++t) recount(t);
-    auto swap_pick = [&](int q, int t1, int t2) {
-      const int ra = res[q][pick[q][t1]], rb = res[q][pick[q][t2]];
-      --cnt[t1][ra]; ++cnt[t1][rb]; --cnt[t2][rb]; ++cnt[t2][ra];
-      const uint8_t x = pick[q][t1];
-      pick[q][t1] = pick[q][t2];
-      pick[q][t2] = x;
-      recount(t1);
-      recount(t2);
-    };
-    auto descend = [&]() {
-      for (int pass = 0; pass < 32; ++pass) {
-        bool improved = false;
-        for (int q = 0; q < nl; ++q)
-          for (int t1 = 0; t1 < NBG; ++t1)
-            for (int t2 = t1 + 1; t2 < NBG; ++t2) {
-              const int ra = res[q][pick[q][t1]], rb = res[q][pick[q][t2]];
-              if (ra == rb) continue;
-              const int a1 = cnt[t1][ra], b1 = cnt[t1][rb], a2 = cnt[t2][ra], b2 = cnt[t2][rb];
-              // step t1: ra -> rb; step t2: rb -> ra
-              const int d = moved_max(t1, a1, b1) + moved_max(t2, b2, a2) - mx[t1] - mx[t2];
-              const int sq = 2 * (b1 - a1) + 2 + 2 * (a2 - b2) + 2;
-              if (d < 0 || (d == 0 && sq < 0)) {
-                swap_pick(q, t1, t2);
-                improved = true;
-              }
-            }
-        if (!improved) break;
-      }
-    };
-    descend();
-    // Alternating-path (Kempe) moves between two steps, which the pairwise descent cannot make: a
-    // lane on a residue that two lanes hit at step t1 swaps its blocks of steps t1 and t2; the
-    // residue it brings to t1 may collide there with another lane, which swaps its t1 / t2 blocks
-    // too, and so on (at most kKempeLen lanes). A chain is kept when the two steps' passes drop,
-    // otherwise undone; then the descent runs again. (config E: passes 1.30 x the per-quarter bound
-    // max(steps, largest residue count) after the descent alone; tools/r4/plan_stats.py)
-    if constexpr (NBG > 1) {
-      auto res_at = [&](int q, int t) { return (int)res[q][pick[q][t]]; };
-      for (int round = 0; round < rounds; ++round) {
-        bool improved = false;
-        for (int t1 = 0; t1 < NBG; ++t1) {
-          for (int r = 0; r < 16; ++r) {
-            if (cnt[t1][r] < 2) continue;
-            int q0 = -1;
-            for (int q = 0; q < nl; ++q)
-              if (res_at(q, t1) == r) { q0 = q; break; }
-            bool done = false;
-            for (int t2 = 0; t2 < NBG && !done; ++t2) {
-              if (t2 == t1) continue;
-              const int before = mx[t1] + mx[t2];
-              int path[kKempeLen], len = 0;
-              int q = q0;
-              while (true) {
-                swap_pick(q, t1, t2);
-                path[len++] = q;
-                const int rn = res_at(q, t1);  // brought from t2
-                if (cnt[t1][rn] < 2 || len == kKempeLen) break;
-                int qn = -1;
-                for (int qq = 0; qq < nl && qn < 0; ++qq) {
-                  if (res_at(qq, t1) != rn) continue;
-                  bool used = false;
-                  for (int l = 0; l < len; ++l) used |= path[l] == qq;
-                  if (!used) qn = qq;
-                }
-                if (qn < 0) break;
-                q = qn;
-              }
-              if (mx[t1] + mx[t2] < before) {
-                done = improved = true;
-              } else {
-                for (int l = len - 1; l >= 0; --l) swap_pick(path[l], t1, t2);
-              }
-            }
-            if (done) break;  // counts changed: rescan from the next step
-          }
-        }
-        if (!improved) break;
-        descend();
-      }
-    }
+    // the aligned order (plan_order.h); rounds > 0 (FA_PLAN_ORDER_SEARCH): with the earlier chain
+    // search before the alignment, and a second start from the equitable colouring
+    plan_order::order_quarter(S, nl, rounds, rounds > 0);
     for (int q = 0; q < nl; ++q) {
       const int part = (p0 + q) % NSPLIT;
       uint16_t v[NBG];
       for (int t = 0; t < NBG; ++t) {
-        const int k = pick[q][t];
+        const int k = plan_order::block_at(S, q, t);
         v[t] = (uint16_t)(((part * NBG + k) << 10) | (base[q] + off[q][k]));
       }
       // one 2-B store each (volatile: not merged into 12- / 16-B stores, whose data registers the

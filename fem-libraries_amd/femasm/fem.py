@@ -659,8 +659,11 @@ def _plan_order(V, fm, adj, fb, plan, sh, eadj=None, order: str = "positional", 
     """Bank-conflict-aware LDS order of the affine-simplex gather (fa_plan_order). order:
     "positional" (default) also balances which entries share a 16-lane quarter (one int32 per
     adjacency entry), "steps" orders each lane's blocks only, "none" keeps the plain slot map.
-    search: also the alternating-path moves (FA_PLAN_ORDER_SEARCH: ~0.5 % faster assemblies on config E
-    for a ~10x longer plan)."""
+    Every quarter gets the aligned order of csrc/plan_order.h: the pairwise descent, then Kempe swaps
+    that bring the over-full residues' extra steps together (the equitable colouring where no residue
+    holds more than a lane has blocks). search (FA_PLAN_ORDER_SEARCH): also the descent's
+    alternating-path chain search and a second start from the equitable colouring (config E: 2 % fewer
+    LDS passes for a ~4x longer plan); DESIGN.md §3.2b has the counts."""
     if order not in ("positional", "steps", "none"):
         raise ValueError(f"unknown slot order {order!r}")
     if order == "none":

@@ -135,9 +135,10 @@ typedef struct {
                                 the edges at vertex 0 (the affine route's error is up to 3x that) */
 #define FA_PLAN_DETERMINISTIC 0x2 /* set by the caller: assemblies with this plan (fa_assemble_matrix and
                                      fa_gather_rows) are deterministic, as with FA_DETERMINISTIC */
-#define FA_PLAN_ORDER_SEARCH 0x4  /* set by the caller before fa_plan_order: also run the alternating-path
-                                     moves of the bank-order search (fewer LDS bank conflicts, config E
-                                     ~0.7 % faster per assembly, plan ~8x slower: 1.5 -> 12 s) */
+#define FA_PLAN_ORDER_SEARCH 0x4  /* set by the caller before fa_plan_order: search the LDS order harder (the
+                                     chain search before the alignment and a second start from the
+                                     equitable colouring, csrc/plan_order.h: config E 2 % fewer LDS passes,
+                                     33.19 vs 33.15 ms per assembly (no gain), plan 1.1 -> 4.8 s) */
 #define FA_PLAN_NEO 0x8           /* set by fa_plan_gather_form for FA_NEO_HOOKEAN: fa_plan_order orders
                                      the slots for the neo-Hookean kernel's item split */
 
