@@ -2901,23 +2901,20 @@ __global__ __launch_bounds__(NT, NN == GD + 1 ? kLinWavesP1 : 4) void k_gather_l
     const int h = (int)(off & 1);
     const int nb = d0.nb;
     const bool valid = jit < d0.na;
-    // The LDS adds are issued by every lane (no branch): a lane without an item of this chunk (or, on
-    // a broken pattern, with a slot past the chunk) adds zeros -- its record's s Ji zeroed -- to an
-    // in-chunk slot of its own. Behind a branch the compiler could not count the outstanding LDS
-    // operations and waited for each block's adds to complete (lgkmcnt(0)) before the next block's
-    // prefetched table word.
-    // (P2 / table blocks: config E 35.2 vs 36.0 ms. P1 simplices keep the branch: C 1.10 vs 1.11 ms,
-    // their items are four table-free blocks)
+    // Table blocks (UNC): a lane without an item of this chunk (or, on a broken pattern, with a slot past
+    // the chunk) sits out the whole unrolled block loop, one lane-divergent region with straight-line
+    // code inside, so its quarter's adds cost no LDS passes (a wholly idle quarter of a chunk's last item
+    // wave had cost NBG x BS2 passes for its zeros). A branch per BLOCK is what must not be: behind one
+    // the compiler could not count the outstanding LDS operations and waited for each block's adds to
+    // complete (lgkmcnt(0)) before the next block's prefetched table word (config E 35.2 vs 36.0 ms,
+    // when every lane added, idle ones zeros). P1 simplices keep the branch per block: C 1.10 vs
+    // 1.11 ms, their items are four table-free blocks.
     constexpr bool UNC = !P1G;
     int smax = 0;
 #pragma unroll
     for (int bb = 0; bb < NBG; ++bb) smax = max(smax, (int)((cur.sl[bb / 2] >> (16 * (bb % 2))) & 1023u));
     bad |= valid && smax >= d0.nb;
     const bool eff = valid && smax < d0.nb;
-    if constexpr (UNC) {
-#pragma unroll
-      for (int kk = 0; kk < BS2; ++kk) cur.r[kk] = eff ? cur.r[kk] : 0.0;
-    }
     if (__any(eff)) {  // wave-uniform: a wave without items (a short chunk's last waves) skips them
       const int aloc = pf0 % NN;
       // the row's packed blocks: one ds_read_b64 per block (nine for a table of doubles)
@@ -2952,108 +2949,109 @@ __global__ __launch_bounds__(NT, NN == GD + 1 ? kLinWavesP1 : 4) void k_gather_l
 #pragma unroll
           for (int k = 0; k < GD; ++k) B[i * GD + k] = fma(P.rlm, N[i * GD + k], N[k * GD + i]);
       };
-      uint64_t qn = 0ull;
-      if constexpr (!P1G) qn = Ah0[(cur.sl[0] >> 10) & 63u];
-      // FIX: the blocks' scale exponents, read together before the adds (one LDS wait, not one per block)
-      // (table blocks only: the fused P1 kernel has no registers to spare)
-      uint32_t ex[FIX ? NBG : 1];
-      if constexpr (FIX && !P1G) {
+      if (!UNC || eff) {  // (UNC: the lane-divergent region; every slot below is inside the chunk)
+        uint64_t qn = 0ull;
+        if constexpr (!P1G) qn = Ah0[(cur.sl[0] >> 10) & 63u];
+        // FIX: the blocks' scale exponents, read together before the adds (one LDS wait, not one per block)
+        // (table blocks only: the fused P1 kernel has no registers to spare)
+        uint32_t ex[FIX ? NBG : 1];
+        if constexpr (FIX && !P1G) {
+#pragma unroll
+          for (int bb = 0; bb < NBG; ++bb) {
+            const int sb = (int)((cur.sl[bb / 2] >> (16 * (bb % 2))) & 1023u);
+            ex[bb] = s_bx[(k & 1) * MAXB + sb];
+          }
+        }
 #pragma unroll
         for (int bb = 0; bb < NBG; ++bb) {
-          const int sb = (int)((cur.sl[bb / 2] >> (16 * (bb % 2))) & 1023u);
-          ex[bb] = s_bx[(k & 1) * MAXB + (eff ? sb : ((tid & 63) < nb ? (tid & 63) : 0))];
-        }
-      }
+          const uint32_t slv = (cur.sl[bb / 2] >> (16 * (bb % 2))) & 0xFFFFu;
+          const int s = (int)(slv & 1023u);
+          const int b = (int)(slv >> 10);
+          double G[GD][GD];
+          if constexpr (P1G) {
+            constexpr double cv = GD == 2 ? 0.5 : 1.0 / 6.0;  // reference simplex volume
+            double gB[GD], dot = 0.0;
 #pragma unroll
-      for (int bb = 0; bb < NBG; ++bb) {
-        const uint32_t slv = (cur.sl[bb / 2] >> (16 * (bb % 2))) & 0xFFFFu;
-        const int s = (int)(slv & 1023u);
-        const int b = (int)(slv >> 10);
-        double G[GD][GD];
-        if constexpr (P1G) {
-          constexpr double cv = GD == 2 ? 0.5 : 1.0 / 6.0;  // reference simplex volume
-          double gB[GD], dot = 0.0;
+            for (int d = 0; d < GD; ++d) {
+              double g0 = 0.0;
 #pragma unroll
-          for (int d = 0; d < GD; ++d) {
-            double g0 = 0.0;
+              for (int kk = 0; kk < GD; ++kk) g0 -= cur.r[kk * GD + d];
 #pragma unroll
-            for (int kk = 0; kk < GD; ++kk) g0 -= cur.r[kk * GD + d];
-#pragma unroll
-            for (int kk = 0; kk < GD; ++kk) g0 = b == kk + 1 ? cur.r[kk * GD + d] : g0;
-            gB[d] = g0;
-            dot = fma(gA[d], g0, dot);
-          }
-          const double ra = cv * P.rlm;
-#pragma unroll
-          for (int i = 0; i < GD; ++i)
-#pragma unroll
-            for (int kk = 0; kk < GD; ++kk) G[i][kk] = fma(ra * gA[i], gB[kk], cv * gB[i] * gA[kk]) + (i == kk ? cv * dot : 0.0);
-        } else {
-        double B[BS2];
-        unpack(qn, B);
-        if (bb + 1 < NBG)  // next block's table entry: issued before this block's atomics
-          qn = Ah0[(cur.sl[(bb + 1) / 2] >> (16 * ((bb + 1) % 2) + 10)) & 63u];
-        // G = (s Ji)^T B (s Ji), column by column; K = G + tr(G) / (1 + r) I
-#pragma unroll
-        for (int dd = 0; dd < GD; ++dd) {
-          double T[GD];
-#pragma unroll
-          for (int i = 0; i < GD; ++i) {
-            double t = B[i * GD] * cur.r[dd];
-#pragma unroll
-            for (int kk = 1; kk < GD; ++kk) t = fma(B[i * GD + kk], cur.r[kk * GD + dd], t);
-            T[i] = t;
-          }
-#pragma unroll
-          for (int e = 0; e < GD; ++e) {
-            double g = cur.r[e] * T[0];
-#pragma unroll
-            for (int i = 1; i < GD; ++i) g = fma(cur.r[i * GD + e], T[i], g);
-            G[e][dd] = g;
-          }
-        }
-        double tr = G[0][0];
-#pragma unroll
-        for (int i = 1; i < GD; ++i) tr += G[i][i];
-        tr *= P.trc;
-#pragma unroll
-        for (int i = 0; i < GD; ++i) G[i][i] += tr;
-        }
-        if (negw) {
-          const double sg = rec_sign(cur.r[BS2]);
-#pragma unroll
-          for (int i = 0; i < GD; ++i)
-#pragma unroll
-            for (int kk = 0; kk < GD; ++kk) G[i][kk] *= sg;
-        }
-        const uint32_t colm = (cur.mask >> (b * GD)) & ((1u << GD) - 1);
-        if (__any((rowm | colm) != 0u)) {
-#pragma unroll
-          for (int i = 0; i < GD; ++i)
-#pragma unroll
-            for (int kk = 0; kk < GD; ++kk)
-              if (((rowm >> i) | (colm >> kk)) & 1u) G[i][kk] = 0.0;
-        }
-        if (UNC || eff) {
-          const int sd = eff ? s : ((tid & 63) < nb ? (tid & 63) : 0);  // (zeros) distinct slots
-          double* ap = acc + h + sd * BS2;
-          if constexpr (FIX) {
-            const double S = pow2(blk_scale(P1G ? s_bx[(k & 1) * MAXB + sd] : ex[bb]));  // the block's scale
+              for (int kk = 0; kk < GD; ++kk) g0 = b == kk + 1 ? cur.r[kk * GD + d] : g0;
+              gB[d] = g0;
+              dot = fma(gA[d], g0, dot);
+            }
+            const double ra = cv * P.rlm;
 #pragma unroll
             for (int i = 0; i < GD; ++i)
 #pragma unroll
-              for (int kk = 0; kk < GD; ++kk) {
-                // round(v * 2^se): v * 2^se + 1.5 * 2^52 has a unit ulp for |v * 2^se| < 2^51, and its
-                // bits minus those of 1.5 * 2^52 are that integer (two's complement)
-                const double t = fma(G[i][kk], S, 0x1.8p52);
-                const unsigned long long q = (unsigned long long)__double_as_longlong(t) - 0x4338000000000000ull;
-                atomicAdd(reinterpret_cast<unsigned long long*>(ap + i * GD + kk), q);
-              }
+              for (int kk = 0; kk < GD; ++kk) G[i][kk] = fma(ra * gA[i], gB[kk], cv * gB[i] * gA[kk]) + (i == kk ? cv * dot : 0.0);
           } else {
+          double B[BS2];
+          unpack(qn, B);
+          if (bb + 1 < NBG)  // next block's table entry: issued before this block's atomics
+            qn = Ah0[(cur.sl[(bb + 1) / 2] >> (16 * ((bb + 1) % 2) + 10)) & 63u];
+          // G = (s Ji)^T B (s Ji), column by column; K = G + tr(G) / (1 + r) I
+#pragma unroll
+          for (int dd = 0; dd < GD; ++dd) {
+            double T[GD];
+#pragma unroll
+            for (int i = 0; i < GD; ++i) {
+              double t = B[i * GD] * cur.r[dd];
+#pragma unroll
+              for (int kk = 1; kk < GD; ++kk) t = fma(B[i * GD + kk], cur.r[kk * GD + dd], t);
+              T[i] = t;
+            }
+#pragma unroll
+            for (int e = 0; e < GD; ++e) {
+              double g = cur.r[e] * T[0];
+#pragma unroll
+              for (int i = 1; i < GD; ++i) g = fma(cur.r[i * GD + e], T[i], g);
+              G[e][dd] = g;
+            }
+          }
+          double tr = G[0][0];
+#pragma unroll
+          for (int i = 1; i < GD; ++i) tr += G[i][i];
+          tr *= P.trc;
+#pragma unroll
+          for (int i = 0; i < GD; ++i) G[i][i] += tr;
+          }
+          if (negw) {
+            const double sg = rec_sign(cur.r[BS2]);
 #pragma unroll
             for (int i = 0; i < GD; ++i)
 #pragma unroll
-              for (int kk = 0; kk < GD; ++kk) atomicAdd(ap + i * GD + kk, G[i][kk]);
+              for (int kk = 0; kk < GD; ++kk) G[i][kk] *= sg;
+          }
+          const uint32_t colm = (cur.mask >> (b * GD)) & ((1u << GD) - 1);
+          if (__any((rowm | colm) != 0u)) {
+#pragma unroll
+            for (int i = 0; i < GD; ++i)
+#pragma unroll
+              for (int kk = 0; kk < GD; ++kk)
+                if (((rowm >> i) | (colm >> kk)) & 1u) G[i][kk] = 0.0;
+          }
+          if (UNC || eff) {
+            double* ap = acc + h + s * BS2;
+            if constexpr (FIX) {
+              const double S = pow2(blk_scale(P1G ? s_bx[(k & 1) * MAXB + s] : ex[bb]));  // the block's scale
+#pragma unroll
+              for (int i = 0; i < GD; ++i)
+#pragma unroll
+                for (int kk = 0; kk < GD; ++kk) {
+                  // round(v * 2^se): v * 2^se + 1.5 * 2^52 has a unit ulp for |v * 2^se| < 2^51, and its
+                  // bits minus those of 1.5 * 2^52 are that integer (two's complement)
+                  const double t = fma(G[i][kk], S, 0x1.8p52);
+                  const unsigned long long q = (unsigned long long)__double_as_longlong(t) - 0x4338000000000000ull;
+                  atomicAdd(reinterpret_cast<unsigned long long*>(ap + i * GD + kk), q);
+                }
+            } else {
+#pragma unroll
+              for (int i = 0; i < GD; ++i)
+#pragma unroll
+                for (int kk = 0; kk < GD; ++kk) atomicAdd(ap + i * GD + kk, G[i][kk]);
+            }
           }
         }
       }
@@ -4413,6 +4411,8 @@ __global__ __launch_bounds__(kOrderThreads) void k_order_slots(const int64_t* __
 // collects many more adds than the quarter has steps; the order search then spreads them over
 // the steps. Writes eperm (position -> entry offset) and eadj (the entries' adjacency values in
 // position order). One thread per chunk.
+// (Exchanging entries between the quarters afterwards, while the summed bound falls, was measured and
+// left out: config E's launch did not move for 0.65 s more plan; DESIGN.md 3.2b "Quarter balance".)
 // The residue histograms and fill counts of a chunk's quarters live in LDS (round 6: a thread's 1 KB
 // array of up to 64 quarters sat in scratch; config E's plan step 0.10 s), sized by MQ quarters: the
 // host picks MQ = 16 when every chunk holds at most 16 quarters (the k_gather_lin / k_gather_neo
