@@ -876,6 +876,11 @@ def _prepared_state(V: FunctionSpace, a, marker, plan, fm, ff, sh):
            None if marker is None else (id(marker), marker._version))
     if key in states:
         return states[key]
+    # A form the library does not prepare is remembered with its Poisson ratio, which decides that (the
+    # uniform-nu kernels' interval); the records themselves do not depend on nu, so a state serves every nu.
+    refused = V.__dict__.setdefault("_unprepared", set())
+    if (key, a.nu) in refused:
+        return None
     for k in [k for k in states if k[4] != xver]:  # records of coordinates that are gone
         del states[k]
     while len(states) >= 3:
@@ -899,6 +904,11 @@ def _prepared_state(V: FunctionSpace, a, marker, plan, fm, ff, sh):
             _lib.check(rc, "fa_prepare_cells")
             st = _Prepared(rec, coef, marker, int(pp.has_bc))
             V._prepared_builds = V._prepared_builds + 1
+    if st is None:
+        if len(refused) >= 16:
+            refused.clear()
+        refused.add((key, a.nu))
+        return None
     states[key] = st
     return st
 
@@ -911,8 +921,13 @@ def assemble_matrix(a, bcs=None, diagonal: float = 1.0, A: MatrixCSR | None = No
     diagonal entries are set to `diagonal`. method: "gather" (row-gather, default) or
     "scatter" (element scatter with FP64 atomics; zeroes A first like MatZeroEntries).
     deterministic: bit-identical values run to run (FA_DETERMINISTIC: exact 64-bit fixed-point
-    sums in the gather; linear elasticity with one Poisson ratio on affine simplices, affine Q1 / Q2
-    quadrilaterals and Q1 hexahedra).
+    sums in the gather; linear elasticity with E per cell and one Poisson ratio -0.99 < nu < 0.49, at the
+    default quadrature rule, on affine simplices, affine Q1 / Q2 quadrilaterals and Q1 hexahedra). Any
+    other form, Poisson ratio or rule raises FemasmError: their kernels sum in floating point.
+    The Poisson ratio also picks the kernel of the default mode: -0.99 < nu < 0.49 (with E per cell) runs the
+    uniform-nu kernels and the prepared cell state, any other nu in (-1, 0.5), or lam / mu per cell, the
+    general lam/mu kernels. A quadrature_degree other than the element's default runs the element scatter
+    (FP64 atomics) under either method. All of them meet the same per-row accuracy.
     plan: gather_plan options (owner, slots, order, locality). check: synchronise and raise if a
     kernel found a pattern entry missing (FA_CHECK_ERRORS).
     """

@@ -358,6 +358,28 @@ int ora_quadrature(int ct, int m, double* pts, double* wts) {
   }
 }
 
+/* Point count of the rule ora_quadrature(ct, m, ...) builds, without building it. */
+int ora_quadrature_count(int ct, int m) {
+  int td = tdim_of(ct);
+  if (m < 1) m = 1;
+  int n = (m + 2) / 2;
+  if (simplex(ct)) {
+    if (m == 1) return 1;
+    if (m == 2) return td == 2 ? 3 : 4;
+    n += 1;
+  }
+  if (n > 32) return 1 << 20; /* (past the 1-D Gauss buffers; far past any caller's arrays) */
+  return td == 2 ? n * n : n * n * n;
+}
+
+/* The rule of an assembly entry point, in its static arrays of ORA_MAXQ points: the point count, or
+ * ORA_E_RULE (nothing written) when the rule has more points than the arrays hold. */
+#define ORA_E_RULE (-9)
+static int entry_rule(int ct, int m, double* pts, double* wts) {
+  if (ora_quadrature_count(ct, m) > ORA_MAXQ) return ORA_E_RULE;
+  return ora_quadrature(ct, m, pts, wts);
+}
+
 /* ---------------------------------------------------------------- geometry */
 /* J[i][k] = sum_v x_v[i] dphi_v[k]; returns det J, fills Jinv (row-major [k][i]). */
 static double jacobian(int gd, int nv, const double* gdphi /*[nv][gd]*/, const double* xv /*[nv][gd]*/,
@@ -654,7 +676,8 @@ int ora_assemble_elasticity(const ora_mesh* M, const double* lam, const double* 
   int tdim = gd;
   if (qdeg < 0) qdeg = simplex(M->cell_type) ? 2 * (M->degree - 1) : 2 * M->degree;
   static double pts[ORA_MAXQ * 3], wq[ORA_MAXQ];
-  int nq = ora_quadrature(M->cell_type, qdeg, pts, wq);
+  int nq = entry_rule(M->cell_type, qdeg, pts, wq);
+  if (nq < 0) return nq;
   double* dphi = (double*)malloc(sizeof(double) * nq * nn * tdim);
   double* gdphi = (double*)malloc(sizeof(double) * nq * nv * tdim);
   if (ora_tabulate(M->cell_type, M->degree, nq, pts, NULL, dphi) != nn) return -2;
@@ -746,7 +769,8 @@ int ora_cell_matrices_elasticity(const ora_mesh* M, const double* lam, const dou
   int gd = M->gdim, nn = M->nn, nv = M->nv, nd = nn * gd;
   if (qdeg < 0) qdeg = simplex(M->cell_type) ? 2 * (M->degree - 1) : 2 * M->degree;
   static double pts[ORA_MAXQ * 3], wq[ORA_MAXQ];
-  int nq = ora_quadrature(M->cell_type, qdeg, pts, wq);
+  int nq = entry_rule(M->cell_type, qdeg, pts, wq);
+  if (nq < 0) return nq;
   double* dphi = (double*)malloc(sizeof(double) * nq * nn * gd);
   double* gdphi = (double*)malloc(sizeof(double) * nq * nv * gd);
   if (ora_tabulate(M->cell_type, M->degree, nq, pts, NULL, dphi) != nn) return -2;
@@ -779,8 +803,10 @@ int ora_assemble_residual(const ora_mesh* M, int kind, const double* lam, const 
   if (kind == 1) qs = 1;
   int qf = 2 * M->degree;
   static double ps[ORA_MAXQ * 3], ws[ORA_MAXQ], pf[ORA_MAXQ * 3], wf[ORA_MAXQ];
-  int nqs = ora_quadrature(M->cell_type, qs, ps, ws);
-  int nqf = ora_quadrature(M->cell_type, qf, pf, wf);
+  int nqs = entry_rule(M->cell_type, qs, ps, ws);
+  if (nqs < 0) return nqs;
+  int nqf = entry_rule(M->cell_type, qf, pf, wf);
+  if (nqf < 0) return nqf;
   double* dphi_s = (double*)malloc(sizeof(double) * nqs * nn * gd);
   double* gdphi_s = (double*)malloc(sizeof(double) * nqs * nv * gd);
   double* phi_f = (double*)malloc(sizeof(double) * nqf * nn);
@@ -861,7 +887,8 @@ int ora_apply_lifting(const ora_mesh* M, int kind, const double* lam, const doub
   int gd = M->gdim, nn = M->nn, nv = M->nv, nd = nn * gd;
   if (qdeg < 0) qdeg = simplex(M->cell_type) ? 2 * (M->degree - 1) : 2 * M->degree;
   static double pts[ORA_MAXQ * 3], wq[ORA_MAXQ];
-  int nq = ora_quadrature(M->cell_type, qdeg, pts, wq);
+  int nq = entry_rule(M->cell_type, qdeg, pts, wq);
+  if (nq < 0) return nq;
   double* dphi = (double*)malloc(sizeof(double) * nq * nn * gd);
   double* gdphi = (double*)malloc(sizeof(double) * nq * nv * gd);
   ora_tabulate(M->cell_type, M->degree, nq, pts, NULL, dphi);
@@ -986,7 +1013,8 @@ int ora_assemble_neohookean(const ora_mesh* M, const double* lam, const double* 
   int gd = M->gdim, nn = M->nn, nv = M->nv, bs = gd, nd = nn * gd;
   if (qdeg < 0) qdeg = simplex(M->cell_type) ? 2 * (M->degree - 1) : 2 * M->degree;
   static double pts[ORA_MAXQ * 3], wq[ORA_MAXQ];
-  int nq = ora_quadrature(M->cell_type, qdeg, pts, wq);
+  int nq = entry_rule(M->cell_type, qdeg, pts, wq);
+  if (nq < 0) return nq;
   double* dphi = (double*)malloc(sizeof(double) * nq * nn * gd);
   double* gdphi = (double*)malloc(sizeof(double) * nq * nv * gd);
   ora_tabulate(M->cell_type, M->degree, nq, pts, NULL, dphi);

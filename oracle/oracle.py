@@ -55,6 +55,7 @@ def lib():
         L.ora_nodes.argtypes = [ctypes.c_int, ctypes.c_int, P]
         L.ora_tabulate.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, P, P, P]
         L.ora_quadrature.argtypes = [ctypes.c_int, ctypes.c_int, P, P]
+        L.ora_quadrature_count.argtypes = [ctypes.c_int, ctypes.c_int]
         L.ora_damage_hook.argtypes = [P, ctypes.c_double, ctypes.c_double, ctypes.c_double, P]
         L.ora_damage_stress.argtypes = [P, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, P]
         L.ora_sparsity.argtypes = [ctypes.c_int64, ctypes.c_int, P, ctypes.c_int64, P, P]
@@ -84,10 +85,25 @@ def nodes(cell_type: int, degree: int) -> np.ndarray:
     return X[:n, : _GDIM[cell_type]].copy()
 
 
+ORA_MAXQ = 256  # fa_oracle.c: the static rule arrays of every assembly entry point
+_E_RULE = -9  # fa_oracle.c ORA_E_RULE
+
+
+def _check(r):
+    """Return code of an ora_* assembly entry: a rule past ORA_MAXQ points is the caller's error."""
+    if r == _E_RULE:
+        raise ValueError(f"quadrature rule has more than ORA_MAXQ = {ORA_MAXQ} points")
+    assert r == 0, r
+
+
 def quadrature(cell_type: int, degree: int):
-    pts = np.zeros((512, 3))
-    w = np.zeros(512)
+    n = lib().ora_quadrature_count(cell_type, degree)
+    if n > ORA_MAXQ:
+        raise ValueError(f"quadrature rule of degree {degree} has more than ORA_MAXQ = {ORA_MAXQ} points")
+    pts = np.zeros((n, 3))
+    w = np.zeros(n)
     nq = lib().ora_quadrature(cell_type, degree, _p(pts), _p(w))
+    assert nq == n
     td = _GDIM[cell_type]
     return np.ascontiguousarray(pts.reshape(-1)[: nq * td].reshape(nq, td)), w[:nq].copy()
 
@@ -166,7 +182,7 @@ def assemble_elasticity(cell_type, degree, cells, geom, x, lam, mu, indptr, indi
         bc = np.ascontiguousarray(bc, dtype=np.int8)
         bcp = _p(bc)
     r = lib().ora_assemble_elasticity(ctypes.byref(m), _p(lam), _p(mu), qdeg, bcp, diag, _p(indptr), _p(indices), _p(vals))
-    assert r == 0, r
+    _check(r)
     return vals
 
 
@@ -185,7 +201,7 @@ def assemble_damage(cells, geom, x, lam, mu, u, dnode, indptr, indices, bc=None,
         bc = np.ascontiguousarray(bc, dtype=np.int8)
         bcp = _p(bc)
     r = lib().ora_assemble_damage(ctypes.byref(m), _p(lam), _p(mu), _p(u), _p(dnode), bcp, diag, _p(indptr), _p(indices), _p(vals))
-    assert r == 0, r
+    _check(r)
     return vals
 
 
@@ -200,7 +216,7 @@ def cell_matrices_elasticity(cell_type, degree, cells, geom, x, lam, mu, qdeg=-1
     A = np.zeros((nc, nd, nd))
     m = _mesh_struct(cell_type, degree, cells, geom, x)
     r = lib().ora_cell_matrices_elasticity(ctypes.byref(m), _p(lam), _p(mu), qdeg, _p(A))
-    assert r == 0, r
+    _check(r)
     return A
 
 
@@ -245,7 +261,7 @@ def assemble_residual(cell_type, degree, cells, geom, x, lam, mu, u=None, f=None
     m = _mesh_struct(cell_type, degree, cells, geom, x)
     r = lib().ora_assemble_residual(ctypes.byref(m), kind, _p(lam), _p(mu), None if u is None else _p(u),
                                     None if d is None else _p(d), None if f is None else _p(f), qdeg, _p(b))
-    assert r == 0
+    _check(r)
     return b
 
 
@@ -265,7 +281,7 @@ def apply_lifting(cell_type, degree, cells, geom, x, lam, mu, b, bc, g, x0=None,
     r = lib().ora_apply_lifting(ctypes.byref(m), kind, _p(lam), _p(mu), None if u is None else _p(u),
                                 None if d is None else _p(d), qdeg, _p(bc), _p(g), None if x0 is None else _p(x0),
                                 alpha, _p(b))
-    assert r == 0
+    _check(r)
     return b
 
 
@@ -285,7 +301,7 @@ def assemble_neohookean(cell_type, degree, cells, geom, x, lam, mu, u, indptr=No
         A = np.zeros((nc, nn * bs, nn * bs))
         r = lib().ora_assemble_neohookean(ctypes.byref(m), _p(lam), _p(mu), _p(u), qdeg, None, diag, None, None, None,
                                           _p(A))
-        assert r == 0
+        _check(r)
         return A
     vals = np.zeros((indices.shape[0], bs, bs))
     bcp = None
@@ -294,7 +310,7 @@ def assemble_neohookean(cell_type, degree, cells, geom, x, lam, mu, u, indptr=No
         bcp = _p(bc)
     r = lib().ora_assemble_neohookean(ctypes.byref(m), _p(lam), _p(mu), _p(u), qdeg, bcp, diag, _p(indptr),
                                       _p(indices), _p(vals), None)
-    assert r == 0, r
+    _check(r)
     return vals
 
 
