@@ -13,14 +13,14 @@
 // included after that; 105: the prepared cell state of femasm.hip, fa_prepare_cells .. fa_gather_rows_prepared;
 // 106: the exterior-facet loads of femasm_facet.hip; 107: the scalar functionals of femasm_scalar.hip,
 // included after it; 108: point location and evaluation, femasm_points.hip; 109: the smoothed-aggregation
-// multigrid kernels of femasm_amg.hip, included last); femasm.hip's own definition is compiled under another,
+// multigrid kernels of femasm_amg.hip; 110: the vertex-graph spread of femasm_graph.hip, included last); femasm.hip's own definition is compiled under another,
 // hidden name.
 #include "../../include/femasm.h"
 #define fa_version __attribute__((visibility("hidden"))) fa_version_assembly
 #include "femasm.hip"
 #undef fa_version
 
-extern "C" int fa_version(void) { return 109; }
+extern "C" int fa_version(void) { return 110; }
 
 // ------------------------------------------------------------------------------------ expressions
 constexpr int EV_LIN = 0, EV_DAMAGE = 1, EV_NEO = 2;
@@ -358,3 +358,6 @@ extern "C" int fa_eval_cells(const fa_mesh* mesh, const fa_form* form, int32_t n
 
 // ------------------------------------------------------------------------------------ algebraic multigrid
 #include "femasm_amg.hip"
+
+// ------------------------------------------------------------------------------------ vertex graph: damage spread
+#include "femasm_graph.hip"

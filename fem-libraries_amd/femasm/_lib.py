@@ -217,6 +217,7 @@ SIGNATURES = {
     "fa_bcsr_mult": (ctypes.c_int, [I64, I64, I32, I32, P, P, P, P, I32, P, P]),
     "fa_bcsr_product": (ctypes.c_int, [I64, I32, I32, I32, P, I64, P, P, P, I64, P, I64, P, P]),
     "fa_csr_row_max": (ctypes.c_int, [I64, P, P, P, P, I64, P, P]),
+    "fa_vertex_spread": (ctypes.c_int, [I64, P, P, P, P, P, I32, D, P]),
     "fa_hbm_probe": (ctypes.c_int, [I32, P, P, I64, P]),
 }
 # entry points whose names carry a digit (the header scan that SIGNATURES is checked against reads

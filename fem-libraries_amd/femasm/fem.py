@@ -2208,3 +2208,159 @@ def assemble_scalar(M, cellwise: bool = False, out: torch.Tensor | None = None) 
         out.data_ptr() if cellwise else None, wk.data_ptr(), wk.numel(), None if cellwise else out.data_ptr(),
         _lib.stream_handle(dev)), "fa_assemble_scalar")
     return out
+
+
+# ---------------------------------------------------------------------------------- damage field
+# The reference's second step: mark the vertices of tagged entities and spread the marks over the vertex
+# graph (FEniCSx/mechanic2d/asym_elasto_damage_model.cc:315-475, MFEM/mechanic2d/asym_elasto_damage_model.cc:
+# 1159-1315). One process owns every vertex here, so the reference's scatter_rev / scatter_fwd exchanges
+# between the passes collapse to nothing.
+def mark_vertices(m: Mesh, dim: int, entities, value: float = 1.0, out: torch.Tensor | None = None) -> torch.Tensor:
+    """A per-vertex float64 field [nv] with ``value`` at every vertex of the given entities of dimension
+    ``dim`` (0 .. tdim) and 0 elsewhere; with ``out`` the values are written into that field instead, the
+    rest of it stays, and it is returned. Entity ids are those of ``mesh.entities(m, dim)`` (vertex indices
+    for dim 0, cell ids for dim = tdim): what ``io.MeshTags.find``, ``read_gmsh_tags(...).find`` and
+    ``locate_entities_boundary`` return. Order and duplicates in ``entities`` do not matter (every writer of
+    a vertex writes the same value). An id outside the mesh's entities raises ValueError before anything is
+    indexed."""
+    from . import mesh as _mesh
+
+    dim = int(dim)
+    if not 0 <= dim <= m.tdim:
+        raise ValueError(f"entities of dimension 0 .. {m.tdim}, not {dim}")
+    dev = m.device
+    nv = m.num_vertices
+    ids = torch.as_tensor(entities, device=dev).reshape(-1)
+    if ids.numel() and (ids.dtype.is_floating_point or ids.dtype in (torch.bool, torch.complex64, torch.complex128)):
+        raise ValueError(f"entity ids are integers, not {ids.dtype}")
+    ids = ids.to(torch.int64)
+    if dim == 0:
+        count, verts = nv, None
+    elif dim == m.tdim:
+        count, verts = m.num_cells, m.cells
+    else:
+        verts = _mesh.entities(m, dim)[0]
+        count = int(verts.shape[0])
+    if ids.numel() and (int(ids.min()) < 0 or int(ids.max()) >= count):
+        raise ValueError(f"entity ids outside [0, {count}) of dimension {dim}")
+    if out is None:
+        out = torch.zeros(nv, dtype=torch.float64, device=dev)
+    elif out.dtype != torch.float64 or out.shape != (nv,) or out.device != dev:
+        raise ValueError(f"out must be a float64 tensor of {nv} entries on {dev}")
+    v = ids if verts is None else verts[ids].reshape(-1).to(torch.int64)
+    out[v] = float(value)
+    return out
+
+
+def _spread_host(indptr: torch.Tensor, indices: torch.Tensor, inv_deg: torch.Tensor, d: torch.Tensor,
+                 iterations: int, threshold: float) -> torch.Tensor:
+    """The spread in torch ops (any device; the definition's arithmetic). Rows are padded to the largest degree
+    with an index that points at an appended 0.0 and summed column by column: x + 0.0 == x exactly for x >= 0,
+    so every row's sum is the sequential one, bit for bit."""
+    nv = int(d.shape[0])
+    deg = indptr[1:] - indptr[:-1]
+    width = int(deg.max()) if nv else 0
+    row = torch.repeat_interleave(torch.arange(nv, dtype=torch.int64, device=d.device), deg)
+    col = torch.arange(indices.shape[0], dtype=torch.int64, device=d.device) - indptr[:-1][row]
+    padded = torch.full((nv, width), nv, dtype=torch.int64, device=d.device)
+    padded[row, col] = indices.to(torch.int64)
+
+    def row_sums(f):
+        fz = torch.cat([f, torch.zeros(1, dtype=f.dtype, device=f.device)])
+        s = torch.zeros_like(f)
+        for k in range(width):
+            s = s + fz[padded[:, k]]
+        return s
+
+    for _ in range(iterations):
+        s = torch.where(d < threshold, row_sums(d), torch.zeros_like(d))
+        d = torch.maximum(s * inv_deg, d)
+        d = torch.maximum(row_sums(d) * inv_deg, d)
+    return d
+
+
+def spread(m: Mesh, d0: torch.Tensor, iterations: int, threshold: float = 0.01) -> torch.Tensor:
+    """``iterations`` spreading iterations of the per-vertex field ``d0`` [nv] (float64, finite, >= 0) on the
+    vertex graph of ``m`` (``mesh.vertex_graph``); ``d0`` is left untouched. With N(v) the neighbours of v in
+    ascending index and r(v) = 1 / |N(v)| (0 for a vertex without neighbours, which keeps its value), one
+    iteration is two Jacobi passes, each reading the previous field only:
+
+      gated   s(v) = sum of d(w), w in N(v), where d(v) < threshold, else 0;   d'(v)  = max(s(v) r(v), d(v))
+      full    s(v) = sum of d'(w), w in N(v);                                  d''(v) = max(s(v) r(v), d'(v))
+
+    The sum starts at 0.0 and adds the neighbours one by one in ascending index, is multiplied by the stored
+    reciprocal and compared: a mesh on the GPU (fa_vertex_spread, one lane per vertex, no atomics), one on
+    the CPU (the same passes in torch ops) and a sequential loop agree bit for bit. ``threshold`` may be
+    ``inf`` (every vertex takes the gated pass) or 0 (none does)."""
+    from . import mesh as _mesh
+
+    nv = m.num_vertices
+    dev = m.device
+    iterations = int(iterations)
+    if iterations < 0:
+        raise ValueError(f"iterations must not be negative ({iterations})")
+    threshold = float(threshold)
+    if threshold != threshold:
+        raise ValueError("threshold is NaN")
+    if not isinstance(d0, torch.Tensor) or d0.dtype != torch.float64 or d0.shape != (nv,) or d0.device != dev:
+        raise ValueError(f"d0 must be a float64 tensor of {nv} entries on {dev}")
+    if nv and not bool((torch.isfinite(d0) & (d0 >= 0)).all()):
+        raise ValueError("d0 must be finite and >= 0")
+    indptr, indices, inv_deg = _mesh._vertex_graph(m)
+    if iterations == 0 or nv == 0 or indices.numel() == 0:
+        return d0.clone()
+    if dev.type != "cuda":
+        return _spread_host(indptr, indices, inv_deg, d0, iterations, threshold)
+    d = d0.contiguous().clone()
+    tmp = torch.empty_like(d)
+    _lib.check(_lib.load().fa_vertex_spread(nv, indptr.data_ptr(), indices.data_ptr(), inv_deg.data_ptr(),
+                                            d.data_ptr(), tmp.data_ptr(), iterations, threshold,
+                                            _lib.stream_handle(dev)), "fa_vertex_spread")
+    return d
+
+
+def damage_field(S: FunctionSpace, entities=None, dim: int = 1, tags=None, values=None, d_max: float = 1.0,
+                 iterations: int | None = None, threshold: float = 0.01, name: str = "d") -> Function:
+    """The reference's damage field on the scalar degree-1 Lagrange space ``S``: ``d_max`` at the vertices of
+    the selected entities (``mark_vertices``), spread over the vertex graph (``spread``); the Function that
+    ``AsymDamage(V, ..., d=d)`` takes. Select either ``entities`` of dimension ``dim`` (ids of
+    ``mesh.entities``), or ``tags`` (an ``io.MeshTags``, whose ``dim`` is used) with ``values``, the list of tag
+    values whose entities are damaged (the reference's ``tag_edges_damaged``).
+
+    ``iterations`` defaults to ``8 * (R + 1)``, the reference's ``8 * (MAX_REFINE + 1)``, with R the length of
+    the mesh's ``parent`` chain: the number of ``mesh.refine`` calls that produced it. A mesh whose parents
+    were dropped (rebuilt from its arrays, or moved without them) has R = 0.
+
+    One process owns every vertex; ``parallel.SlabProblem`` and multi-rank ownership are not served."""
+    if not isinstance(S, FunctionSpace) or S.family in ("DG", "Discontinuous Lagrange"):
+        raise ValueError("the damage field lives on a scalar degree-1 Lagrange space, not a DG space")
+    if S.bs != 1:
+        raise ValueError(f"the damage field lives on a scalar space (block size 1, not {S.bs})")
+    if S.degree != 1:
+        raise ValueError(f"the damage field lives on a degree-1 space (node i is vertex i), not degree {S.degree}")
+    m = S.mesh
+    if S.dofmap is not m.cells:
+        raise ValueError("the space's dofmap is not the mesh's cells: its nodes are not the mesh's vertices")
+    if (entities is None) == (tags is None):
+        raise ValueError("pass either entities or tags (with values), not both and not neither")
+    d_max = float(d_max)
+    if not d_max > 0 or d_max == float("inf"):
+        raise ValueError(f"d_max must be positive and finite ({d_max})")
+    if iterations is None:
+        R, p = 0, m.parent
+        while p is not None:
+            R, p = R + 1, p.parent
+        iterations = 8 * (R + 1)
+    elif int(iterations) < 0:
+        raise ValueError(f"iterations must not be negative ({iterations})")
+    if tags is not None:
+        if values is None:
+            raise ValueError("tags need values: the tag values whose entities are damaged")
+        dim = tags.dim
+        vals = [values] if isinstance(values, int) else list(values)
+        found = [tags.find(v).to(m.device).to(torch.int64) for v in vals]
+        entities = torch.cat(found) if found else torch.zeros(0, dtype=torch.int64, device=m.device)
+    elif values is not None:
+        raise ValueError("values select among tags: pass tags with them")
+    d0 = mark_vertices(m, dim, entities, d_max)
+    return Function(S, name, spread(m, d0, int(iterations), threshold))

@@ -249,6 +249,52 @@ def entities(mesh: Mesh, dim: int):
     return out
 
 
+def _vertex_graph(mesh: Mesh):
+    """(indptr, indices, inv_deg) of ``vertex_graph``, built once per mesh; ``inv_deg[v]`` is ``1 / deg(v)`` in
+    float64 and 0 where vertex v has no neighbour (an orphan node of a Gmsh file)."""
+    cached = mesh.__dict__.get("_vgraph")
+    if cached is not None:
+        return cached
+    nv = mesh.num_vertices
+    if nv > _INT32_MAX:
+        raise ValueError(f"the mesh has {nv} vertices: more than the int32 indices of the vertex graph hold")
+    ev, _ = entities(mesh, 1)  # rows (a, b), a < b, in lexicographic order
+    dev = ev.device
+    a, b = ev[:, 0], ev[:, 1]
+    ne = int(ev.shape[0])
+    fwd, bwd = torch.bincount(a, minlength=nv), torch.bincount(b, minlength=nv)
+    deg = fwd + bwd
+    indptr = torch.zeros(nv + 1, dtype=torch.int64, device=dev)
+    indptr[1:] = torch.cumsum(deg, 0)
+    # Row v is its backward neighbours (the a of the edges (a, v)) and then its forward ones (the b of the
+    # edges (v, b)), each in edge order: both parts ascend, and every backward neighbour is below v, every
+    # forward one above. The edges with first vertex v are consecutive; a stable sort of the second column
+    # makes those with second vertex v consecutive and keeps their first vertices in edge order.
+    e = torch.arange(ne, dtype=torch.int64, device=dev)
+    indices = torch.empty(2 * ne, dtype=torch.int32, device=dev)
+    fstart = torch.cumsum(fwd, 0) - fwd
+    indices[indptr[a] + bwd[a] + (e - fstart[a])] = b.to(torch.int32)
+    order = torch.argsort(b, stable=True)
+    bs = b[order]
+    bstart = torch.cumsum(bwd, 0) - bwd
+    indices[indptr[bs] + (e - bstart[bs])] = a[order].to(torch.int32)
+    degf = deg.to(torch.float64)
+    inv_deg = torch.where(deg > 0, 1.0 / degf, torch.zeros_like(degf))
+    out = (indptr, indices, inv_deg)
+    mesh.__dict__["_vgraph"] = out
+    return out
+
+
+def vertex_graph(mesh: Mesh):
+    """The vertex graph of the mesh as CSR, ``(indptr [nv + 1] int64, indices [nnz] int32)``: vertices v and w
+    are neighbours when they share an edge of ``entities(mesh, 1)`` (any cell type; a quadrilateral's or a
+    hexahedron face's diagonal is no edge). Row v lists the neighbours of v in ascending index, without
+    duplicates or self loops, so ``nnz = 2 * num_edges``; a vertex no cell uses has an empty row. Built with
+    torch ops on the mesh's device and cached on the mesh, as ``entities`` is."""
+    indptr, indices, _ = _vertex_graph(mesh)
+    return indptr, indices
+
+
 def exterior_facets(mesh: Mesh) -> torch.Tensor:
     """Facet ids (entities(mesh, tdim - 1)) that belong to exactly one cell (dolfinx
     exterior_facet_indices on one process)."""

@@ -725,6 +725,32 @@ int fa_cheb_step6(int64_t nnodes, const double* Dinv, const double* b, const dou
 int fa_csr_row_max(int64_t nrows, const int64_t* indptr, const int32_t* indices, const int8_t* free_nodes /* or NULL */,
                    const int64_t* in, int64_t nin, int64_t* out, void* stream);
 
+/* ---- vertex graph: the damage field's spread (femasm_graph.hip, fa_version() >= 110) ----
+ * The reference builds its damage field d from tagged edges before it assembles the damage law: the tagged
+ * entities' vertices are set to d_max and the marks are spread over the vertex graph (FEniCSx/mechanic2d/
+ * asym_elasto_damage_model.cc:315-475, MFEM/mechanic2d/asym_elasto_damage_model.cc:1159-1315). On one
+ * process, without its ownership bookkeeping, that is the definition below.
+ *
+ * G is the vertex graph as CSR: indptr [nverts + 1], indices [indptr[nverts]] (int32), row v the neighbours
+ * N(v) of vertex v in ascending index, no self loops, no duplicates; inv_deg[v] = 1 / |N(v)|, and 0 where
+ * N(v) is empty (such a vertex keeps its value). One iteration is two Jacobi passes, each reading only the
+ * previous field and writing a new one:
+ *   gated   s(v) = sum over w in N(v) of d(w) if d(v) < threshold, else 0;   d'(v)  = max(s(v) * inv_deg[v], d(v))
+ *   full    s(v) = sum over w in N(v) of d'(w);                              d''(v) = max(s(v) * inv_deg[v], d'(v))
+ * The arithmetic is part of the definition: s starts at 0.0 and adds the row in its stored order, the sum
+ * is multiplied by the stored reciprocal (not divided by the degree), then the maximum is taken; no product
+ * is followed by an add, so no FMA forms, and a sequential loop over the same arrays gives the same bits.
+ *
+ * d [nverts] holds the start field (finite, >= 0) and receives the result; tmp [nverts] is scratch. One lane
+ * per vertex, 2 * iterations launches on `stream` that alternate d -> tmp (gated) and tmp -> d (full).
+ * Asynchronous, no allocation, no atomics, no LDS, 64-bit index arithmetic; an index outside [0, nverts) is
+ * skipped, never dereferenced. threshold may be +inf (every vertex takes the gated pass) or 0 (none does).
+ * nverts == 0 or iterations == 0 launches nothing and succeeds. Checked on the host before anything is
+ * launched: nverts < 0, iterations < 0 or a null pointer: FA_E_ARG; nverts > INT32_MAX: FA_E_CAPACITY. */
+int fa_vertex_spread(int64_t nverts, const int64_t* indptr, const int32_t* indices, const double* inv_deg,
+                     double* d /* in: start field; out: result */, double* tmp /* [nverts] scratch */,
+                     int32_t iterations, double threshold, void* stream);
+
 /* Measurement helper (not part of the reference interface): a 16-B-per-lane grid-stride stream
  * over n doubles (n even, 16-B aligned buffers) for the measured HBM peak beside the 8 TB/s spec
  * (SURVEY.md section 8(d)). mode 0: dst = src (copy), 1: dst = 1.0 (write only), 2: read src
